@@ -25,17 +25,26 @@ is row-partitioned over the N ranks (strong scaling, BASELINE config 4: 1024 x
 There is no data-path collective; value = all cells x steps / max-over-ranks
 time between barriers.
 
-The timed region is a whole number of fused launches, at least MIN_LAUNCHES,
-covering --steps, and (with the automatic depth) a multiple of 384 steps, so
-every N times the same steps of the same grid; the JSON carries
+A plain run (`--gpus 1 --steps N --warmup W`) does only what the headline
+needs: it sets up, warms up (W steps, and at least two whole launches: the
+first reads the initial depths, the second is the first of the timed kernel
+instance), times exactly N steps (whole launches of the fused depth, then
+one shorter launch for the rest), writes the last timed step's outputs when
+--dump-outputs DIR is given (dump_outputs) and prints the line.
+
+--full adds everything else the bench measures or checks, outside the timed
+region: the GPU-vs-oracle parity check (the numpy oracle on a sample, melt-out
+flips held to the fp64 baseline of the same sample, tests/harness.py
+flip_rule), the C and numpy CPU baselines, the drop-in legs and (--pcie) the
+host-fed leg.  Its timed region is a whole number of fused launches, at least
+MIN_LAUNCHES, covering --steps, and (with the automatic depth) a multiple of
+768 steps, so every N times the same steps of the same grid; the JSON carries
 `steps_requested` beside the timed `steps`.
 
-Prints ONE JSON line on rank 0.  Roofline: achieved = algorithmic bytes per
-fused launch / mean launch time (HIP events on the engine's stream); traffic
+Prints ONE JSON line on rank 0.  Roofline: achieved = algorithmic bytes of the
+timed launches / their time (HIP events on the engine's stream); traffic
 = PMC bytes from the committed profile, only when it was measured on the same
-device code (roofline.traffic_source).  Parity spot check: GPU vs the numpy
-oracle on a sample, melt-out flips held to the fp64 baseline of the same
-sample (tests/harness.py flip_rule).
+device code (roofline.traffic_source).
 """
 
 from __future__ import annotations
@@ -170,6 +179,52 @@ def timed_steps(requested: int, fuse: int, explicit: bool) -> int:
     need = max(requested, MIN_LAUNCHES * max(FUSE_BIG, FUSE_MID, FUSE_SMALL))
     return -(-need // STEP_QUANTUM) * STEP_QUANTUM
 
+
+def launch_plan(steps: int, fuse: int) -> list[int]:
+    """The launches of a plain run's timed region: exactly `steps` steps, as
+    whole launches of the fused depth and one shorter launch for the rest."""
+    return [fuse] * (steps // fuse) + ([steps % fuse] if steps % fuse else [])
+
+
+DUMP_BYTES = 60 << 20  # of the 64 MB a dump may take: the six outputs' share
+
+
+def dump_sample(n: int, elem: int, seed: int) -> np.ndarray | None:
+    """The cells a dump keeps of an n-cell shard whose outputs are `elem`-byte
+    values: None (all of them) while the six outputs fit DUMP_BYTES, else one
+    cell from each of m equal strata of the shard, drawn with the run's seed
+    (the same cells in every run of the same arguments)."""
+    m = DUMP_BYTES // (len(HIST) * elem)
+    if n <= m:
+        return None
+    lo = np.arange(m, dtype=np.int64) * n // m
+    hi = (np.arange(m, dtype=np.int64) + 1) * n // m
+    return lo + (np.random.default_rng(seed).random(m) * (hi - lo)).astype(np.int64)
+
+
+def dump_outputs(eng, args, torch, out_dir: Path, rank: int, world: int) -> dict:
+    """--dump-outputs: what the timed path computed in its last step, as a
+    caller of the engine receives it: the six outputs of the newest history
+    slot (dump_sample's cells, in the engine's own precision) as
+    DIR/<name>.npy, and the shard's mass-balance integrals after that step
+    (tfg_get_diag, [catchments][6] f64) as DIR/mass_balance.npy.  Ranks of a
+    multi-GPU run write <name>.rank<r>.npy."""
+    out_dir.mkdir(parents=True, exist_ok=True)
+    f64 = args.engine == "float64"
+    idx = dump_sample(eng.n, 8 if f64 else 4, args.seed)
+    buf = torch.empty(eng.n, dtype=torch.float64 if f64 else torch.float32, device=f"cuda:{eng.device}")
+    pick = None if idx is None else torch.from_numpy(idx).to(buf.device)
+    tag = "" if world == 1 else f".rank{rank}"
+    for v in HIST:
+        eng.get_field_device(v, buf)
+        a = (buf if pick is None else buf[pick]).cpu().numpy()
+        np.save(out_dir / f"{v}{tag}.npy", a)
+    np.save(out_dir / f"mass_balance{tag}.npy", np.asarray(eng.diagnostics(), dtype=np.float64))
+    del buf, pick
+    return {"dir": str(out_dir), "step": eng.step_index, "cells": eng.n if idx is None else len(idx),
+            "of_cells": eng.n, "dtype": "float64" if f64 else "float32",
+            "arrays": [*HIST, "mass_balance"]}
+
 BASE_CFG = {
     "site_prefix": "synthetic", "forcing_file": "synthetic", "dt": 1, "start_time": "2013032000",
     "end_time": "2014032000", "da": 0.0001, "slope": 50.0, "aspect": 180.0, "lon": -121.81418,
@@ -181,8 +236,16 @@ BASE_CFG = {
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=480)
+    ap.add_argument("--steps", type=int, default=480,
+                    help="timed steps: exactly this many (whole launches of the fused depth, then one shorter launch "
+                         "for the rest); with --full the whole-launch region of timed_steps() covering them")
     ap.add_argument("--warmup", type=int, default=96)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the GPU-vs-oracle parity check, the CPU baselines, the drop-in legs "
+                         "and (--pcie) the host-fed leg; times whole launches, at least MIN_LAUNCHES (timed_steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the six outputs of the last timed step (a fixed, seeded "
+                         "sample of the cells above 64 MB) and the mass-balance integrals as DIR/<name>.npy")
     ap.add_argument("--ny", type=int, default=8192, help="global rows (strong) or rows per GPU (weak)")
     ap.add_argument("--nx", type=int, default=8192)
     ap.add_argument("--frames", type=int, default=24)
@@ -231,7 +294,14 @@ def parse():
     ap.add_argument("--conduction", action="store_true",
                     help="the optional lateral heat-conduction term: Qc re-evaluated (with the one-row halo swap "
                          "between ranks) before every fused launch, inside the timed region")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    extra = [f for f, on in (("--pcie", args.pcie), ("--dropin-queued", args.dropin_queued),
+                             ("--dropin-clean", args.dropin_clean)) if on]
+    if extra and not args.full:
+        ap.error(f"{', '.join(extra)}: a leg of the full run; add --full")
+    return args
 
 
 _T0 = time.perf_counter()
@@ -947,7 +1017,7 @@ def main(args=None):
     # the parity check's GPU side: the handle's first launches (a one-step
     # lead-in, then one whole launch of the timed depth over the whole shard)
     cap = None
-    if not args.no_parity:
+    if args.full and not args.no_parity:
         cap = capture_parity(eng, args, plan, world, torch, local)
         note(f"parity launches done ({eng.step_index} steps)")
     # warmup (untimed): the requested steps, and at least one whole launch of
@@ -958,17 +1028,24 @@ def main(args=None):
     # parity launches count, but the host reads that follow them leave the GPU
     # idle (the first timed launch then ran 5-11 ms long at 8192^2,
     # profiles/r4e_bench_driver_traced.json), so one more whole launch runs
-    # right before the timed region.
+    # right before the timed region.  A plain run, whose first launch is the
+    # instance that reads the initial depths, warms two whole launches at least:
+    # the second is the first of the timed instance.
     warm_steps = warmup_steps(args.warmup, args.fuse)
-    eng.run(max(warm_steps - (eng.step_index - 1), args.fuse) if cap else warm_steps)
-    warm_run = eng.step_index
-    barrier()
-    ns_before = eng.nan_safe_launches() if args.engine == "float32" else 0
-    # Whole fused launches, and at least MIN_LAUNCHES of them, so that a short
-    # --steps still gives a multi-launch timed region; the JSON carries the
-    # requested count beside the timed one.
-    steps = timed_steps(args.steps, args.fuse, fuse_explicit)
-    n_launch = steps // args.fuse
+    if cap:
+        warm_now = max(warm_steps - (eng.step_index - 1), args.fuse)
+    else:
+        warm_now = warm_steps if args.full else max(warm_steps, 2 * args.fuse)
+    # A plain run times exactly --steps: whole launches and one shorter one for
+    # the rest.  --full: whole fused launches, and at least MIN_LAUNCHES of them,
+    # so that a short --steps still gives a multi-launch timed region; the JSON
+    # carries the requested count beside the timed one.
+    if args.full:
+        steps = timed_steps(args.steps, args.fuse, fuse_explicit)
+        launches = [args.fuse] * (steps // args.fuse)
+    else:
+        steps, launches = args.steps, launch_plan(args.steps, args.fuse)
+    n_launch = len(launches)
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_launch)]
     # A split engine (tfg_set_split: a grid of <= 2^24 cells as two parts on two
     # streams) overlaps one part's launch with the other's: per-launch events on
@@ -980,6 +1057,15 @@ def main(args=None):
     # runs at most two calls ahead of the device -- a tenth of config 2's 80 ms region
     gc.collect()
     gc.disable()
+    # The warm-up is queued last, after all the host work above, so the device is
+    # busy until the barrier that opens the timed region returns.  With that host
+    # work (a collector pass among it) between the warm-up and the barrier, the
+    # first timed launch at 8192^2 ran 70.0 ms against 65.6 ms for the later ones;
+    # in this order 66.7-66.9 ms against 65.5-66.3 ms (two boxes, one run each
+    # way): a short timed region then weighs its first launch less.
+    eng.run(warm_now)
+    warm_run = eng.step_index
+    ns_before = eng.nan_safe_launches() if args.engine == "float32" else 0  # a host-side count
     barrier()
     t0 = time.perf_counter()
     for i in range(n_launch):
@@ -987,7 +1073,7 @@ def main(args=None):
             conduct()
         if not split or i == 0:
             ev[i][0].record(stream)
-        eng.run(args.fuse)
+        eng.run(launches[i])
         if not split:
             ev[i][1].record(stream)
     if split:
@@ -996,20 +1082,24 @@ def main(args=None):
     barrier()
     elapsed = time.perf_counter() - t0
     gc.enable()
-    note(f"timed region: {n_launch} launches of {args.fuse} steps in {elapsed:.3f} s")
-    if split:
-        launch_ms = np.full(n_launch, ev[0][0].elapsed_time(ev[-1][1]) / n_launch)
+    note(f"timed region: {steps} steps in {n_launch} launches of at most {args.fuse} in {elapsed:.3f} s")
+    if split:  # the span shared out by each launch's steps (equal launches: span / launches)
+        launch_ms = ev[0][0].elapsed_time(ev[-1][1]) * np.array(launches, dtype=np.float64) / steps
     else:
         launch_ms = np.array([a.elapsed_time(b) for a, b in ev])
     cells = rows * args.nx
     diag = allreduce_diagnostics(eng.diagnostics()) if pg else eng.diagnostics()
-    bytes_launch = cells * launch_bytes_per_cell(args.fuse, elem, args.catchments > 0, args.conduction)
-    achieved = bytes_launch / (float(launch_ms.mean()) / 1e3) / 1e9
+    # algorithmic bytes of all timed launches over their time (equal launches: one launch's over the mean)
+    bytes_timed = cells * sum(launch_bytes_per_cell(k, elem, args.catchments > 0, args.conduction) for k in launches)
+    achieved = bytes_timed / (float(launch_ms.sum()) / 1e3) / 1e9
     # launches of the timed region that ran the fp32 step's NaN-safe form (0: the clean form was timed)
     ns_timed = (eng.nan_safe_launches() - ns_before) if args.engine == "float32" else None
-    # the host-fed leg, the drop-in legs and the CPU baseline run on rank 0 at N=1 only (BASELINE contract)
-    pcie = pcie_inclusive(eng, args, torch) if world == 1 and args.pcie else None
-    dropin_grid = dropin_grid_leg(eng, args, torch, stream) if world == 1 and not args.no_dropin else None
+    dumped = dump_outputs(eng, args, torch, Path(args.dump_outputs), rank, world) if args.dump_outputs else None
+    # the host-fed leg, the drop-in legs and the CPU baseline run on rank 0 at N=1 only (BASELINE contract),
+    # and only in a --full run
+    pcie = pcie_inclusive(eng, args, torch) if args.full and world == 1 and args.pcie else None
+    dropin_grid = (dropin_grid_leg(eng, args, torch, stream) if args.full and world == 1 and not args.no_dropin
+                   else None)
     eng.close()
     torch.cuda.empty_cache()
     # every rank checks its own shard's first rows against the oracle (outside the timed region)
@@ -1036,15 +1126,16 @@ def main(args=None):
     result = None
     if rank == 0:
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             note("CPU baseline (C oracle)")
             cpu = cpu_baseline(args)
         dropin_many = None
-        if world == 1 and not args.no_dropin and args.dropin_instances > 0:
+        if args.full and world == 1 and not args.no_dropin and args.dropin_instances > 0:
             note("drop-in leg: defer_update instances")
             dropin_many = dropin_instances_leg(args, local)
         if world > 1:
-            parity = parity_summary([r["sample_parity"] for r in ranks["ranks"]]) if not args.no_parity else None
+            parity = (parity_summary([r["sample_parity"] for r in ranks["ranks"]])
+                      if args.full and not args.no_parity else None)
         traffic, traffic_source = pmc_traffic(rows, args)
         result = {
             "metric": METRIC,
@@ -1067,7 +1158,10 @@ def main(args=None):
                 f"the opening barrier weighs ~1 %)"
                 + ("" if fuse_explicit else f", and a multiple of {STEP_QUANTUM} steps so that every GPU count "
                                             f"times the same work")),
-            "launches": {"count": n_launch, "steps_each": args.fuse, "ms_min": float(launch_ms.min()),
+            "full": args.full,
+            "outputs_dumped": dumped,
+            "launches": {"count": n_launch, "steps_each": launches[0], "steps_last": launches[-1],
+                         "ms_min": float(launch_ms.min()),
                          "ms_mean": float(launch_ms.mean()), "ms_max": float(launch_ms.max()),
                          "ms_each": [round(float(x), 3) for x in launch_ms]},
             "warmup": args.warmup,
@@ -1099,7 +1193,7 @@ def main(args=None):
                 "frac": achieved / HBM_PEAK_GBS,
                 "traffic": traffic,
                 "traffic_source": traffic_source,
-                "bytes_per_cell_update": bytes_launch / (cells * args.fuse),
+                "bytes_per_cell_update": bytes_timed / (cells * steps),
                 "kernel_ms_per_launch": float(launch_ms.mean()),
                 "launch_time_source": ("HIP events on the engine's stream: the span of the timed region (the second "
                                        "part joined) / launches; split launches, two parts on two streams "

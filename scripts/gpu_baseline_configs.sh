@@ -5,7 +5,7 @@ set -o pipefail
 cd $GRAFT_REPO_ROOT
 OUT=gpurun_out/configs; mkdir -p $OUT
 run() { name=$1; shift
-  timeout -k 10 600 python bench.py "$@" > $OUT/$name.log 2>&1 || { echo "$name FAILED"; tail -5 $OUT/$name.log; return 1; }
+  timeout -k 10 600 python bench.py --full "$@" > $OUT/$name.log 2>&1 || { echo "$name FAILED"; tail -5 $OUT/$name.log; return 1; }
   grep '^{' $OUT/$name.log | tail -1 > $OUT/$name.json
   python3 -c "import json; r=json.load(open('$OUT/$name.json')); print('$name', '%.2f G cell-updates/s'%(r['value']/1e9), '%.0f GB/s'%r['roofline']['achieved'], 'frac %.3f'%r['roofline']['frac'], 'ms/launch %.2f'%r['roofline']['kernel_ms_per_launch'])"; }
 run cfg2_1024sq_year      --ny 1024 --nx 1024 --steps 8760 --warmup 120 --fuse 120 --no-pcie &&

@@ -8,19 +8,20 @@ cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 TAG=${TAG:-prof}
 mkdir -p gpurun_out/$TAG
+OUT=${TFG_OUT_DIR:-bench_out}/$TAG; mkdir -p $OUT  # the bench lines and traces of this script
 if [ -z "$SKIP_PMC" ]; then
   PMC_TAG=$TAG/pmc PMC_PROFILE=gpurun_out/$TAG/pmc_8192x8192_fuse128.json bash scripts/gpu_pmc.sh || exit $?
   cp gpurun_out/$TAG/pmc_8192x8192_fuse128.json profiles/pmc_8192x8192_fuse128.json
 fi
 echo "== rocprof kernel trace of the driver's bench"
-timeout -k 10 600 rocprofv3 --kernel-trace --stats -d gpurun_out/$TAG/trace -o run --output-format csv -- python3 bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/$TAG/bench_traced.log 2>&1; rc=$?; echo "prof rc=$rc"
+timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/trace -o run --output-format csv -- python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_traced.log 2>&1; rc=$?; echo "prof rc=$rc"
 [ $rc -eq 0 ] || exit $rc
-python3 scripts/trace_summary.py gpurun_out/$TAG/trace gpurun_out/$TAG/bench_traced.log gpurun_out/$TAG/trace_summary.json
+python3 scripts/trace_summary.py $OUT/trace $OUT/bench_traced.log $OUT/trace_summary.json
 echo "== bench (driver command)"
-timeout -k 10 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/$TAG/bench_driver.log 2>&1; rc=$?; echo "bench rc=$rc"
-grep '^{' gpurun_out/$TAG/bench_driver.log | cut -c1-300
+timeout -k 10 600 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver.log 2>&1; rc=$?; echo "bench rc=$rc"
+grep '^{' $OUT/bench_driver.log | cut -c1-300
 [ $rc -eq 0 ] || exit $rc
 echo "== bench (no flags)"
-timeout -k 10 600 python3 bench.py > gpurun_out/$TAG/bench_default.log 2>&1; rc=$?; echo "bench rc=$rc"
-grep '^{' gpurun_out/$TAG/bench_default.log | cut -c1-300
+timeout -k 10 600 python3 bench.py --full > $OUT/bench_default.log 2>&1; rc=$?; echo "bench rc=$rc"
+grep '^{' $OUT/bench_default.log | cut -c1-300
 exit $rc

@@ -7,6 +7,7 @@ cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 TAG=${TAG:-verify}
 mkdir -p gpurun_out/$TAG
+OUT=${TFG_OUT_DIR:-bench_out}/$TAG; mkdir -p $OUT  # the bench lines and traces of this script
 export TFG_REPORT_DIR=gpurun_out/$TAG/reports
 echo "== gpu tests"
 timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread -p no:cacheprovider \
@@ -16,8 +17,8 @@ echo "== smoke"
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/$TAG/smoke.log 2>&1; rc=$?; echo "smoke rc=$rc"; tail -2 gpurun_out/$TAG/smoke.log
 [ $rc -eq 0 ] || exit $rc
 echo "== bench as the driver runs it"
-timeout -k 10 600 python bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/$TAG/bench_driver.log 2>&1; rc=$?; echo "bench rc=$rc"; grep '^{' gpurun_out/$TAG/bench_driver.log | cut -c1-400
+timeout -k 10 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver.log 2>&1; rc=$?; echo "bench rc=$rc"; grep '^{' $OUT/bench_driver.log | cut -c1-400
 [ $rc -eq 0 ] || exit $rc
 echo "== bench default"
-timeout -k 10 600 python bench.py > gpurun_out/$TAG/bench_default.log 2>&1; rc=$?; echo "bench rc=$rc"; grep '^{' gpurun_out/$TAG/bench_default.log | cut -c1-400
+timeout -k 10 600 python bench.py --full > $OUT/bench_default.log 2>&1; rc=$?; echo "bench rc=$rc"; grep '^{' $OUT/bench_default.log | cut -c1-400
 exit $rc

@@ -142,9 +142,107 @@ def test_weak_scaling_stays_behind_its_flag():
     assert p[3]["row0"] == 3 * 8192 and p[3]["rows"] == 8192 and p[0]["workload"] == "32768x8192 grid (8192x8192 per GPU)"
 
 
+def test_plain_run_times_exactly_the_requested_steps():
+    """Without --full, --steps is the number of timed steps: whole launches of
+    the fused depth, then one shorter launch for the rest (none when the depth
+    divides the count, one short launch when the count is below the depth)."""
+    bench, args = _args("--gpus", "1", "--steps", "300", "--warmup", "5")
+    assert not args.full and args.dump_outputs is None
+    assert bench.launch_plan(300, 128) == [128, 128, 44] and bench.launch_plan(256, 128) == [128, 128]
+    assert bench.launch_plan(20, 128) == [20] and bench.launch_plan(1, 1) == [1]
+    for steps, k in ((1, 384), (383, 384), (385, 384), (480, 128), (2304, 256)):
+        plan = bench.launch_plan(steps, k)
+        assert sum(plan) == steps and all(0 < x <= k for x in plan) and all(x == k for x in plan[:-1])
+
+
+def test_legs_of_the_full_run_are_refused_without_it():
+    """--pcie, --dropin-queued and --dropin-clean add legs that only a --full
+    run has: alone they are an argument error, not a flag silently ignored."""
+    for flag in ("--pcie", "--dropin-queued", "--dropin-clean"):
+        with pytest.raises(SystemExit):
+            _args(flag)
+        _, args = _args("--full", flag)
+        assert args.full
+    with pytest.raises(SystemExit):
+        _args("--steps", "0")
+
+
+def test_dump_sample_is_fixed_by_the_seed_and_fits_the_budget():
+    """--dump-outputs keeps every cell of a small shard, and of a large one a
+    strictly increasing sample, one cell per stratum, the same for the same
+    seed, whose six arrays stay under 64 MB (fp32 and fp64 outputs alike)."""
+    bench, _ = _args()
+    assert bench.dump_sample(250 * 1000, 4, 1) is None
+    n = 8192 * 8192
+    for elem in (4, 8):
+        a, b, c = bench.dump_sample(n, elem, 7), bench.dump_sample(n, elem, 7), bench.dump_sample(n, elem, 8)
+        assert np.array_equal(a, b) and not np.array_equal(a, c)
+        assert a.dtype == np.int64 and a[0] >= 0 and a[-1] < n and np.all(np.diff(a) > 0)
+        assert 32e6 < len(a) * elem * len(bench.HIST) <= 64e6 - 1e6  # room for the mass-balance integrals
+    m = (60 << 20) // 24  # one more cell than fit: the first shard size that is sampled
+    s = bench.dump_sample(m + 1, 4, 3)
+    assert len(s) == m and s[-1] <= m and np.all(np.diff(s) > 0)
+
+
+@pytest.mark.gpu
+def test_plain_run_dumps_the_outputs_of_its_last_timed_step(tmp_path):
+    """A plain run (no --full) on an odd-sized grid of two launch depths' worth
+    of steps plus two: it times exactly --steps, runs none of the full run's
+    legs, and --dump-outputs writes what a caller of the engine reads after the
+    same launches (two warm-up launches, the first of which reads the initial
+    depths, then 24 + 24 + 2 timed steps), bit for bit, as float32 arrays of
+    every cell, beside the mass-balance integrals."""
+    from topoflow_glacier.bmi.config import TopoflowGlacierConfig
+    from topoflow_glacier.engine import GlacierEngine
+    from topoflow_glacier.synthetic import diurnal_table
+
+    ny, nx, k = 250, 1000, 24
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--ny", str(ny), "--nx", str(nx), "--steps", "50",
+           "--warmup", "5", "--fuse", str(k), "--dump-outputs", str(tmp_path / "out")]
+    r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 50 and d["steps_requested"] == 50 and d["steps_note"] is None and d["full"] is False
+    assert d["launches"]["count"] == 3 and d["launches"]["steps_each"] == k and d["launches"]["steps_last"] == 2
+    assert d["warmup_steps_run"] == 2 * k and d["nan_safe_timed_launches"] == 0
+    assert d["value"] > 0 and d["unit"] == "cell-updates/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert abs(d["value"] - ny * nx * 50 / (d["ms_per_step"] * 50 / 1e3)) <= 1e-9 * d["value"]
+    rf = d["roofline"]  # 50 steps in three launches: 50 x 52 + 3 x 120 algorithmic bytes per cell
+    assert abs(rf["bytes_per_cell_update"] - (50 * 52 + 3 * 120) / 50) < 1e-12 and rf["achieved"] > 0
+    for leg in ("cpu_baseline", "cpu_baseline_numpy_1core", "pcie_inclusive", "dropin_per_step_grid",
+                "dropin_defer_update_instances", "sample_parity"):
+        assert d[leg] is None, leg
+    assert "parity" not in r.stderr and "CPU baseline" not in r.stderr
+    od = d["outputs_dumped"]
+    assert od["cells"] == od["of_cells"] == ny * nx and od["step"] == 2 * k + 50 and od["dtype"] == "float32"
+    bench, args = _args()
+    cfg = TopoflowGlacierConfig.model_validate(dict(bench.BASE_CFG, ny=ny, nx=nx, dt=1.0))
+    eng = GlacierEngine(cfg, ny, nx, engine="float32", device=0, n_frames=args.frames, hist_depth=k, fuse_steps=k)
+    try:
+        eng.fill_synthetic(args.seed, diurnal_table(args.frames), nx_global=nx)
+        for n in (k, k, k, k, 2):
+            eng.run(n)
+        eng.sync()
+        want = {v: eng.get_field(v, dtype=np.float32) for v in bench.HIST}
+        want["mass_balance"] = np.asarray(eng.diagnostics(), dtype=np.float64)
+    finally:
+        eng.close()
+    names = sorted(p.name for p in (tmp_path / "out").iterdir())
+    assert names == sorted(f"{v}.npy" for v in want)
+    total = 0
+    for v, w in want.items():
+        got = np.load(tmp_path / "out" / f"{v}.npy")
+        total += got.nbytes
+        assert got.dtype == w.dtype and got.shape == w.shape and np.array_equal(got, w), v
+        assert np.all(np.isfinite(got))
+    assert total <= 64e6 and np.any(want["h_snow"] > 0) and want["mass_balance"][0, 0] > 0
+
+
 @pytest.mark.gpu
 def test_bench_prints_one_json_line_with_the_contract_keys():
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--ny", "256", "--nx", "1024", "--steps", "48", "--warmup", "24",
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--full", "--ny", "256", "--nx", "1024", "--steps", "48", "--warmup", "24",
            "--fuse", "24", "--cpu-cells", "4096", "--cpu-steps", "48", "--parity-cells", "2048",
            "--dropin-instances", "64", "--dropin-queued", "--dropin-clean"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300)
@@ -197,7 +295,7 @@ def test_bench_parity_holds_at_the_deep_launches_of_the_multi_gpu_lines():
     melt onsets, which the GPU suite's rules explain (tests/harness.py
     depletion_steps, melt_onsets).  One 384-step launch over 64 x 1024 cells,
     checked the way each rank of those lines checks its own rows."""
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--ny", "64", "--nx", "1024", "--fuse", "384", "--steps", "768",
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--full", "--ny", "64", "--nx", "1024", "--fuse", "384", "--steps", "768",
            "--warmup", "0", "--no-cpu-baseline", "--no-dropin"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=280)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -264,7 +362,7 @@ def test_bare_gpus_two_runs_two_ranks():
 
     env = dict(os.environ, TFG_BENCH_ONE_DEVICE="1", TFG_BENCH_BACKEND="gloo")
     env.pop("WORLD_SIZE", None)
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--ny", "512", "--nx", "1024", "--steps", "48",
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--full", "--gpus", "2", "--ny", "512", "--nx", "1024", "--steps", "48",
            "--warmup", "24", "--fuse", "24"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -301,8 +399,8 @@ def test_multi_rank_line_is_self_verifying():
 
     env = dict(os.environ, TFG_BENCH_ONE_DEVICE="1", TFG_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-           "127.0.0.1", "--master-port", "29531", str(ROOT / "bench.py"), "--gpus", "2", "--ny", "512", "--nx", "1024",
-           "--steps", "48", "--warmup", "24", "--fuse", "24"]
+           "127.0.0.1", "--master-port", "29531", str(ROOT / "bench.py"), "--full", "--gpus", "2", "--ny", "512", "--nx",
+           "1024", "--steps", "48", "--warmup", "24", "--fuse", "24"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
