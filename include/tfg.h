@@ -309,8 +309,12 @@ int tfg_set_flux(tfg_handle* h, int flux);
  * parts of about half the cells each, the second on a second stream of its own
  * with its own copy of the step uniforms: one part's next launch fills the other
  * part's drain (+4-5 % at 1024^2 and 4096^2; none at 8192^2, which runs one part).
- * Results are the same bit for bit (the update is pointwise; each part's
- * workgroups fold their diagnostics into the slab rows of their own cells).
+ * Outputs and state are the same bit for bit (the update is pointwise).  The
+ * mass-balance diagnostics are the same bit for bit while both parts run one
+ * workgroup per 256-cell chunk, as the unsplit launch does (each part's
+ * workgroups fold into the slab rows of their own cells); a grid with more
+ * chunks than slab rows gives workgroups several chunks, and the diagnostics
+ * then agree to fp64 rounding (1e-12 relative, tests/test_gpu_diagnostics.py).
  *   TFG_SPLIT_AUTO  (default) split fp32-engine grids of 2^18 (one round of the
  *                   resident workgroups) to 2^24 cells
  *   TFG_SPLIT_OFF   one launch over the whole grid

@@ -480,6 +480,62 @@ def catchment_diag(syn: dict, m, cid: np.ndarray, nsteps: int, n_frames: int, n_
     return out
 
 
+def bare_ice_inputs(seed: int, ny: int, nx: int, n_frames: int = 24, row0: int = 0):
+    """The synthetic workload with every third cell (cell % 3 == 0) bare, dry
+    ice: no initial snow and no precipitation in any frame, so the exact-zero
+    snow gate of the ice melt (:1424) never moves there and the ice-melt
+    integral is non-zero and well conditioned (tests/test_gpu_diagnostics.py).
+    Returns (static dict of [ncell] fp64, forcing dict of [n_frames][ncell]
+    fp64), every value fp32-exact, as the engines consume it."""
+    syn, _ = synthetic_inputs(seed, ny, nx, n_frames, row0=row0)
+    bare = (np.arange(ny * nx) + row0 * nx) % 3 == 0
+    static = {k: np.array(syn[s], dtype=np.float64) for k, s in (("elev", "elev"), ("slope", "slope"), ("aspect", "aspect"),
+              ("h0_snow", "h_snow"), ("h0_ice", "h_ice"), ("h0_swe", "h_swe"), ("h0_iwe", "h_iwe"))}
+    static["h0_snow"][bare] = 0.0
+    static["h0_swe"][bare] = 0.0
+    forcing = {k: np.array(syn[k], dtype=np.float64) for k in ("P", "T_air", "Hum_sp", "P_air", "uz")}
+    forcing["P"][:, bare] = 0.0
+    return static, forcing
+
+
+def catchment_fsum(cid: np.ndarray, per_cell: np.ndarray, n_catch: int) -> np.ndarray:
+    """[n_catch] exactly rounded sums (math.fsum) of per_cell [..., ncell] over
+    each catchment's cells and every leading axis; 0 for a catchment without
+    cells.  The summation error of a comparison is then the engine's alone."""
+    import math
+
+    cid = np.asarray(cid).reshape(-1)
+    v = np.asarray(per_cell, dtype=np.float64).reshape(-1, cid.size)
+    order = np.argsort(cid, kind="stable")
+    bounds = np.searchsorted(cid[order], np.arange(n_catch + 1))
+    v = np.ascontiguousarray(v[:, order].T)  # [ncell sorted by catchment][leading]
+    return np.array([math.fsum(v[bounds[c]:bounds[c + 1]].ravel().tolist()) for c in range(n_catch)])
+
+
+def fp32_forcing_sums(P: np.ndarray, T_air: np.ndarray, T_rain_snow: float, launches) -> np.ndarray:
+    """The fp32 engine's per-cell precipitation sums, emulated exactly:
+    [n_launches][3][ncell] fp64 holding, per launch, the steps' P, rain
+    (P where T_air > T_rain_snow, else 0) and snow (the complement) added
+    sequentially in np.float32 in step order (tfg::DiagF).  P, T_air:
+    [nsteps][ncell] fp32-exact; `launches`: the steps per launch, in order."""
+    P = np.asarray(P, dtype=np.float32)
+    assert np.isfinite(T_air).all(), "a NaN T_air is neither rain nor snow: not emulated here"
+    rain = np.asarray(T_air, dtype=np.float64) > float(T_rain_snow)
+    out = np.zeros((len(launches), 3, P.shape[1]))
+    k = 0
+    for j, K in enumerate(launches):
+        s = np.zeros((3, P.shape[1]), dtype=np.float32)
+        for _ in range(K):
+            zero = P[k] * np.float32(0.0)  # NaN stays NaN, as the kernel's P * 0.0f
+            s[0] = s[0] + P[k]
+            s[1] = s[1] + np.where(rain[k], P[k], zero)
+            s[2] = s[2] + np.where(rain[k], zero, P[k])
+            k += 1
+        out[j] = s.astype(np.float64)
+    assert k == P.shape[0], "launches must cover the steps"
+    return out
+
+
 def oracle_diag(m) -> np.ndarray:
     """[1][6] diagnostics row of an oracle model (vol_P, PR, PS, SM, IM, P_max)."""
     return np.array([[m.vol_P, m.vol_PR, m.vol_PS, m.vol_SM, m.vol_IM, m.P_max]], dtype=np.float64)

@@ -21,7 +21,8 @@ import pandas as pd
 import pytest
 import yaml
 
-from tests.harness import (BASE_CFG, FLUX_F64_ENGINE, GOLDEN, OUT_NAMES, c_oracle_hist, flip_rule, fp64_baseline_flips,
+from tests.harness import (BASE_CFG, FLUX_F64_ENGINE, GOLDEN, OUT_NAMES, bare_ice_inputs, c_oracle_hist, flip_rule,
+                           fp64_baseline_flips,
                            gpu_run_fields, load_golden, make_engine, melt_out_flips, oracle_run, parity,
                            run_gpu_vs_oracle, split_engine, synthetic_inputs, valid_mask)
 
@@ -455,25 +456,47 @@ def test_device_generator_matches_host_mirror():
     e.close()
 
 
-def test_catchment_diagnostics():
+@pytest.mark.parametrize("inputs", ["synthetic", "bare_ice"])
+def test_catchment_diagnostics(inputs):
     """Per-catchment mass-balance reduction (segmented wave reduction) vs
-    the oracle's per-catchment sums."""
+    the oracle's per-catchment sums.  On the synthetic workload no cell's ice
+    melts in 20 steps (the vol_IM check holds zeros); "bare_ice" is the same
+    workload with every third cell bare, dry ice (harness.bare_ice_inputs),
+    whose ice-melt integral is non-zero in every catchment."""
     ny, nx, nsteps, seed, nc = 16, 48, 20, 4, 5
     syn, d = synthetic_inputs(seed, ny, nx, 24)
     cid = ((np.arange(ny)[:, None] // 4) + (np.arange(nx)[None, :] // 17) * 2) % nc
     cid = cid.astype(np.int32).reshape(-1)
+    frames = np.arange(nsteps) % 24
     e = make_engine(BASE_CFG, ny, nx, "float32", n_frames=24, hist_depth=nsteps, n_catch=nc)
-    e.fill_synthetic(seed, d)
-    e.set_field("catch_id", cid)
+    if inputs == "synthetic":
+        e.fill_synthetic(seed, d)
+        e.set_field("catch_id", cid)
+        forcing = {k: syn[k][frames].astype(np.float64) for k in ("P", "T_air", "Hum_sp", "P_air", "uz")}
+        static = {k: np.asarray(syn[s], dtype=np.float64) for k, s in (("elev", "elev"), ("slope", "slope"), ("aspect", "aspect"),
+                  ("h0_snow", "h_snow"), ("h0_ice", "h_ice"), ("h0_swe", "h_swe"), ("h0_iwe", "h_iwe"))}
+    else:
+        static, fr = bare_ice_inputs(seed, ny, nx, 24)
+        forcing = {k: v[frames] for k, v in fr.items()}
+        for k in ("elev", "slope", "aspect"):
+            e.set_field(k, static[k])
+        for k in ("h_snow", "h_ice", "h_swe", "h_iwe"):
+            e.set_field(k, static["h0_" + k[2:]])
+        e.set_field("catch_id", cid)
+        e.init_state()
+        for f in range(24):
+            for k, v in fr.items():
+                e.set_field(k, v[f], index=f)
     e.run(nsteps)
     e.sync()
     diag = e.diagnostics()
     e.close()
-    frames = np.arange(nsteps) % 24
-    forcing = {k: syn[k][frames].astype(np.float64) for k in ("P", "T_air", "Hum_sp", "P_air", "uz")}
-    static = {k: np.asarray(syn[s], dtype=np.float64) for k, s in (("elev", "elev"), ("slope", "slope"), ("aspect", "aspect"),
-              ("h0_snow", "h_snow"), ("h0_ice", "h_ice"), ("h0_swe", "h_swe"), ("h0_iwe", "h_iwe"))}
     ref, m = oracle_run(BASE_CFG, static, forcing, nsteps)
+    if inputs == "bare_ice":
+        # the exact-zero snow gate of the ice melt moves in no cell, and ice melts in every catchment
+        zero = np.vstack([static["h0_swe"][None] == 0, ref["h_swe"] == 0])
+        assert (zero == zero[0]).all()
+        assert np.bincount(cid, weights=m.cell_vol_IM, minlength=nc).min() > 0
     da_m2 = BASE_CFG["da"] * 1e6
     for c in range(nc):
         sel = cid == c
@@ -487,6 +510,8 @@ def test_catchment_diagnostics():
     # before update_swe / update_iwe clamp the outputs)
     for col, v in ((3, "SM"), (4, "IM")):
         want = np.bincount(cid, weights=np.broadcast_to(getattr(m, "cell_vol_" + v), cid.shape), minlength=nc)
+        if inputs == "bare_ice":
+            assert want.max() > 0, v
         assert np.all(np.abs(diag[:, col] - want) <= 1e-5 * np.maximum(np.abs(want), np.abs(want).max())), (v, diag[:, col], want)
     assert _rel(diag[:, 3].sum(), m.vol_SM) < 1e-5
     assert _rel(diag[:, 4].sum(), m.vol_IM) < 1e-5

@@ -7,7 +7,10 @@ The update is pointwise (no term couples cells, bmi_topoflow_glacier.py
 :413-465), so a split run must equal the one-launch run bit for bit: every
 history output of every step, the fp64 state, and -- since each part's
 workgroups fold into the slab rows of their own 256-cell chunks, one
-workgroup per chunk as unsplit -- the mass-balance diagnostics.  The API calls
+workgroup per chunk as unsplit -- the mass-balance diagnostics.  (Only at
+these sizes: a grid with more chunks than slab rows gives a workgroup several
+chunks, split or not, and its diagnostics then agree to fp64 rounding;
+tests/test_gpu_diagnostics.py holds that case to 1e-12.)  The API calls
 between launches (field reads, sets, diagnostics) order the handle's stream
 after the second part; the grids below are not multiples of the 256-cell chunk,
 so the second part ends in padding."""

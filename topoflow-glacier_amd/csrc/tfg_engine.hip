@@ -49,7 +49,8 @@ using namespace tfg_kern;
 // thread 0 writes the state, the window slot, the history slot, the frame, the
 // eight outputs into the pinned host block, the diagnostic slab row and the
 // release flag.  Same arithmetic as k_fused<double, true, ...> with K = 1, so
-// the same results bit for bit; the per-launch fixed work (LDS bins, the
+// the same outputs and state bit for bit (the diagnostics to fp64 rounding,
+// see k_cell_run); the per-launch fixed work (LDS bins, the
 // read-back of the history slot, host-memory reads of inputs and uniforms) is
 // gone from the critical path.
 struct CellIo {
@@ -175,8 +176,13 @@ __global__ __launch_bounds__(64 * tfg::kCellWaves) void k_cell(const KArgs a, co
 // bulk runs of one catchment): k_cell's lane-batched step in a loop, the state
 // in registers, each step's frame values, window slot and uniforms requested
 // one step ahead (a one-slot window runs one step per launch, tfg_step).
-// Same arithmetic as k_fused<double, true, ...>, so the same results bit for
-// bit.  Every thread stores the same values to the same addresses, so no
+// Same arithmetic as k_fused<double, true, ...>, so the same outputs and state
+// bit for bit.  The diagnostics agree to fp64 rounding only (1e-12 relative,
+// tests/test_gpu_diagnostics.py): the one-cell kernels scale every step's terms
+// by da dt (cell_step_exact_wave), k_fused sums them unscaled over a launch and
+// scales once (diag_scale), so the fp64 grid's own diagnostics also move in
+// their last bits with the launch partition.  Every thread stores the same
+// values to the same addresses, so no
 // store sits behind a branch and each wave reads back only window slots it
 // wrote itself.
 __global__ __launch_bounds__(64 * tfg::kCellWaves) void k_cell_run(const KArgs a, const tfg_uniforms* __restrict__ uni,
@@ -1316,21 +1322,25 @@ int tfg_set_field(tfg_handle* h, int field, int index, const void* src, int src_
   if (is_hist_field(field) && (index < 0 || index >= h->hist_depth)) return fail(h, TFG_ERR_ARG, "history slot out of range");
   if (field == TFG_ST_CATCH_ID) {
     if (src_dtype != TFG_I32) return fail(h, TFG_ERR_ARG, "catchment ids must be TFG_I32");
-    if (!h->catch_id) {
-      HIPCHK(h, hipMalloc((void**)&h->catch_id, (size_t)h->n_pad * 4));
-      HIPCHK(h, hipMemsetAsync(h->catch_id, 0, (size_t)h->n_pad * 4, h->stream));
-    }
-    HIPCHK(h, hipMemcpyAsync(h->catch_id, src, (size_t)n * 4, src_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+    // the ids index the kernels' LDS bins: they are validated before anything
+    // reaches h->catch_id (a host source in place, a device source from a
+    // staged host copy), so a rejected map leaves the handle as it was
     std::vector<int32_t> tmp;
     const int32_t* hs = static_cast<const int32_t*>(src);
     if (src_on_device) {
       tmp.resize(n);
       HIPCHK(h, hipMemcpyAsync(tmp.data(), src, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
+      HIPCHK(h, hipStreamSynchronize(h->stream));
       hs = tmp.data();
     }
-    HIPCHK(h, hipStreamSynchronize(h->stream));
     for (int64_t i = 0; i < n; ++i)
       if (hs[i] < 0 || hs[i] >= h->n_catch) return fail(h, TFG_ERR_ARG, "catchment id out of [0, n_catch)");
+    if (!h->catch_id) {
+      HIPCHK(h, hipMalloc((void**)&h->catch_id, (size_t)h->n_pad * 4));
+      HIPCHK(h, hipMemsetAsync(h->catch_id, 0, (size_t)h->n_pad * 4, h->stream));
+    }
+    HIPCHK(h, hipMemcpyAsync(h->catch_id, src, (size_t)n * 4, src_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     return TFG_OK;
   }
   if (src_dtype != TFG_F32 && src_dtype != TFG_F64) return fail(h, TFG_ERR_ARG, "src dtype must be TFG_F32/TFG_F64");
@@ -1663,7 +1673,6 @@ int launch_steps(tfg_handle* h, const tfg_uniforms* d_u, const tfg_uniforms* u, 
       a.n = h->n;
       a.n_pad = h->n_pad;
       a.n_step = h->n_pad;
-  a.n_step = h->n_pad;
       a.io_in = nullptr;
       a.io_out = nullptr;
       a.io_flag = nullptr;
