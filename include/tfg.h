@@ -265,6 +265,26 @@ int tfg_set_fuse(tfg_handle* h, int max_steps_per_launch);
 int tfg_get_diag(tfg_handle* h, double* out, int n_catch);
 int tfg_reset_diag(tfg_handle* h);
 
+/* Per-catchment sums of one output field over history slots, reduced on the
+ * device: out[nslots][n_catch] (fp64),
+ *   out[j][c] = sum over the cells i with catch_id[i] == c of
+ *               field[slot (hist0 + j) % hist_depth][i],
+ * unscaled, accumulated in fp64.  The rows follow the ring, so the slots of
+ * consecutive steps read back in step order.  `field` is one of the six
+ * history fields (TFG_OUT_H_SNOW, _SM, _H_ICE, _IM, _M_TOTAL, _RH), as the
+ * steps wrote them; 0 <= hist0 < hist_depth and 1 <= nslots <= hist_depth.
+ * Without a catchment-id raster every cell counts for catchment 0.  A
+ * catchment without cells reads 0; a NaN cell makes exactly its (slot,
+ * catchment) entry NaN.  No floating-point atomics: a row is the same bit for
+ * bit whichever other slots share the call.
+ * out_on_device == 0: `out` is host memory and the call blocks.  Otherwise
+ * `out` is a device pointer and the call is queued on the handle's stream
+ * (after the second part of a split launch), without a host wait.
+ * Replaces: the runoff series of a caller of the reference, M_total * da_m2
+ * per step (examples/run_topoflow_glacier.py:112), summed over a catchment's
+ * cells -- with TFG_OUT_M_TOTAL, times da_m2, a hydrograph per catchment. */
+int tfg_catchment_series(tfg_handle* h, int field, int hist0, int nslots, double* out, int out_on_device);
+
 /* Wait for all work queued on the handle's stream. */
 int tfg_sync(tfg_handle* h);
 

@@ -495,6 +495,7 @@ __global__ void k_terrain(const R* __restrict__ elev, const double* __restrict__
 
 
 #include "tfg_flow.hpp"  // the optional ice-flow kernels (tfg_ice_flow_*)
+#include "tfg_series.hpp"  // per-catchment sums of history planes (tfg_catchment_series)
 
 // tfg_set_inputs / tfg_get_outputs: the per-step BMI traffic of one call each.
 // src [5][n]: P_air, Hum_sp, P, T_air, uz (BMI order) -> frame planes.
@@ -618,6 +619,9 @@ struct tfg_handle {
   void* hist = nullptr;
   double* diag = nullptr;        // [n_catch][6]
   double* slab = nullptr;        // [max_blocks][n_catch][6]
+  // tfg_catchment_series, allocated on first use: the workgroups' partial sums and a host call's result
+  double* series_part = nullptr; // [series_blocks][kSeriesBatch][n_catch]
+  double* series_out = nullptr;  // [hist_depth][n_catch]
   float* d_diurnal = nullptr;
   int32_t* d_flag = nullptr;
   tfg_uniforms* d_u = nullptr;
@@ -1080,7 +1084,7 @@ int tfg_abi_version(void) { return TFG_ABI_VERSION; }
 #if !defined(__HIP_DEVICE_COMPILE__)
 __attribute__((used)) static const char tfg_build_tag[] =
     "libtfg abi=" TFG_STR(TFG_ABI_VERSION) " arch=gfx950 (hipcc) tfg-src-sha256=" TFG_SRC_HASH
-    "; kernels: k_fused<float|double,exact|fast,...>, k_cell, k_cell_run, k_cell_many, k_diag_reduce, k_fill_synthetic";
+    "; kernels: k_fused<float|double,exact|fast,...>, k_cell, k_cell_run, k_cell_many, k_diag_reduce, k_catch_series, k_fill_synthetic";
 
 const char* tfg_build_info(void) { return tfg_build_tag; }
 #else
@@ -1212,7 +1216,7 @@ int tfg_destroy(tfg_handle* h) {
   if (h->side) (void)hipStreamSynchronize(h->side);
   void* ptrs[] = {h->forc, h->stat, h->lwsw, h->geo, h->catch_id, h->st, h->tot, h->ring, h->hist, h->diag, h->wtmp, h->halo,
                   h->flow_halo, h->flow_edges, h->flow_red, h->qc, h->cond_halo, h->cond_edges,
-                  h->slab, h->d_diurnal, h->d_flag, h->d_u, h->d_u2, h->staging};
+                  h->slab, h->series_part, h->series_out, h->d_diurnal, h->d_flag, h->d_u, h->d_u2, h->staging};
   for (void* q : ptrs) if (q) (void)hipFree(q);
   for (int i = 0; i < 2; ++i) {
     if (h->h_u[i]) (void)hipHostFree(h->h_u[i]);
@@ -1786,6 +1790,53 @@ int tfg_get_diag(tfg_handle* h, double* out, int n_catch) {
   HIPCHK(h, hipStreamSynchronize(h->stream));
   // P_max of an empty history is 0 like the reference's initial P_max (:314)
   for (int c = 0; c < n_catch; ++c) if (out[c * 6 + 5] == -INFINITY) out[c * 6 + 5] = 0.0;
+  return TFG_OK;
+}
+
+int tfg_catchment_series(tfg_handle* h, int field, int hist0, int nslots, double* out, int out_on_device) {
+  if (int rc_ = api_sync(h)) return rc_;  // after a split launch's second part
+  if (!h) return fail(nullptr, TFG_ERR_ARG, "null handle");
+  if (!out) return fail(h, TFG_ERR_ARG, "null out");
+  if (!is_hist_field(field))
+    return fail(h, TFG_ERR_ARG, "catchment series: field " + std::to_string(field) +
+                                    " is not a history field (h_snow, SM, h_ice, IM, M_total, RH)");
+  if (hist0 < 0 || hist0 >= h->hist_depth) return fail(h, TFG_ERR_ARG, "catchment series: first history slot out of range");
+  if (nslots < 1 || nslots > h->hist_depth) return fail(h, TFG_ERR_ARG, "catchment series: slot count outside 1..hist_depth");
+  HIPCHK(h, hipSetDevice(h->device));
+  const int blocks = series_blocks(h->n, h->n_catch);
+  const int row_len = kSeriesBatch * h->n_catch;
+  if (!h->series_part) HIPCHK(h, hipMalloc((void**)&h->series_part, (size_t)blocks * row_len * 8));
+  if (!out_on_device && !h->series_out)
+    HIPCHK(h, hipMalloc((void**)&h->series_out, (size_t)h->hist_depth * h->n_catch * 8));
+  double* dout = out_on_device ? out : h->series_out;
+  int fdt = 0;
+  const void* plane = field_ptr(h, field, 0, &fdt);  // slot 0's plane of the field, engine type
+  const int64_t stride = (int64_t)kNumHist * h->n_pad;
+  const size_t lds = (size_t)row_len * 8;
+  for (int j0 = 0; j0 < nslots; j0 += kSeriesBatch) {
+    const int nb = std::min(kSeriesBatch, nslots - j0);
+    const int slot0 = (hist0 + j0) % h->hist_depth;
+    auto launch = [&](auto kern, auto* pl) {
+      hipLaunchKernelGGL(kern, blocks, kBlock, lds, h->stream, pl, stride, h->hist_depth, slot0, nb, h->catch_id, h->n,
+                         h->n_catch, h->series_part);
+    };
+    if (h->engine == TFG_F32) {
+      if (h->catch_id) launch(k_catch_series<float, true>, (const float*)plane);
+      else launch(k_catch_series<float, false>, (const float*)plane);
+    } else {
+      if (h->catch_id) launch(k_catch_series<double, true>, (const double*)plane);
+      else launch(k_catch_series<double, false>, (const double*)plane);
+    }
+    HIPCHK(h, hipGetLastError());
+    const int nent = nb * h->n_catch;
+    hipLaunchKernelGGL(k_series_reduce, (nent + 15) / 16, kBlock, 0, h->stream, h->series_part, blocks, row_len, nent,
+                       dout + (int64_t)j0 * h->n_catch);
+    HIPCHK(h, hipGetLastError());
+  }
+  if (!out_on_device) {
+    HIPCHK(h, hipMemcpyAsync(out, dout, (size_t)nslots * h->n_catch * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+  }
   return TFG_OK;
 }
 

@@ -107,6 +107,7 @@ def load() -> ctypes.CDLL:
         "tfg_set_fuse": ([vp, i32], i32),
         "tfg_get_diag": ([vp, dp, i32], i32),
         "tfg_reset_diag": ([vp], i32),
+        "tfg_catchment_series": ([vp, i32, i32, i32, vp, i32], i32),
         "tfg_sync": ([vp], i32),
         "tfg_fill_synthetic": ([vp, ctypes.c_uint64, i64, i64, ctypes.POINTER(ctypes.c_float), i32], i32),
         "tfg_last_error": ([vp], ctypes.c_char_p),
@@ -298,5 +299,5 @@ def exported_symbols() -> list[str]:
         "tfg_fill_synthetic", "tfg_last_error", "tfg_terrain_from_dem", "tfg_ice_flow_edges", "tfg_ice_flow_dmax", "tfg_ice_flow_step", "tfg_ice_flow_run", "tfg_set_inputs", "tfg_get_outputs",
         "tfg_update", "tfg_update_many", "tfg_conduction_edges", "tfg_conduction_update", "tfg_conduction_off",
         "tfg_nan_safe_launches", "tfg_set_step_form", "tfg_set_flux", "tfg_set_split", "tfg_join", "tfg_get_split",
-        "tfg_selftest_powers",
+        "tfg_selftest_powers", "tfg_catchment_series",
     ) if hasattr(L, n)]

@@ -104,6 +104,8 @@ class GlacierEngine:
             import torch
 
             t = values.contiguous()
+            if name == "catch_id":
+                self._catch_cells = None  # catchment_cells() counts the new raster
             code = {4: nat.F32, 8: nat.F64}[t.element_size()] if name != "catch_id" else nat.I32
             if t.numel() != self.n:
                 raise ValueError(f"{name}: {t.numel()} values for {self.n} cells")
@@ -114,6 +116,7 @@ class GlacierEngine:
             self.sync()
             return
         if name == "catch_id":
+            self._catch_cells = None  # catchment_cells() counts the new raster
             a = np.ascontiguousarray(np.broadcast_to(np.asarray(values, dtype=np.int32), (self.n,)))
             code = nat.I32
         else:
@@ -229,6 +232,11 @@ class GlacierEngine:
     @property
     def last_hist(self) -> int:
         return (self.step_index - 1) % self.hist_depth if self.step_index > 0 else 0
+
+    @property
+    def torch_device(self) -> str:
+        """The engine's GPU as a torch device string."""
+        return f"cuda:{self.device}"
 
     def init_state(self) -> None:
         """initialize()-time state from the depth rasters (reference :389-395)."""
@@ -501,6 +509,64 @@ class GlacierEngine:
 
     def reset_diagnostics(self) -> None:
         self._chk(self.lib.tfg_reset_diag(self.h))
+
+    def catchment_cells(self) -> np.ndarray:
+        """[n_catch] cells of each catchment of this shard, from the id raster
+        (np.bincount, cached until catch_id is set again); without a raster
+        the whole grid is catchment 0."""
+        if getattr(self, "_catch_cells", None) is None:
+            try:
+                cells = np.bincount(self.get_field("catch_id"), minlength=self.n_catch)
+            except nat.NativeError as e:
+                if e.code != nat.ERR_STATE:  # ERR_STATE: no catchment-id raster set
+                    raise
+                cells = np.zeros(self.n_catch, dtype=np.int64)
+                cells[0] = self.n
+            self._catch_cells = cells
+        return self._catch_cells
+
+    def catchment_series(self, name: str = "M_total", first: int | None = None, count: int | None = None,
+                         reduce: str = "sum", out=None):
+        """[count][n_catch] float64: per catchment, the sum (or, reduce="mean",
+        the mean over the catchment's cells; 0 for a catchment without cells)
+        of an output field in `count` consecutive history slots from slot
+        `first`, following the ring (tfg_catchment_series: reduced on the
+        device, the planes stay there).  Defaults: the slots of the last
+        min(step_index, hist_depth) steps, in step order.  With "M_total",
+        times da_m2, a row is the step's runoff [m3 s-1] per catchment
+        (examples/run_topoflow_glacier.py:112).
+
+        `out` may be a contiguous float64 torch CUDA tensor of count * n_catch
+        elements on the engine's device (sums only): the call is then queued
+        on the engine's stream without a host wait, under get_field_device's
+        stream rules -- torch's current stream is drained first, and the caller
+        sync()s (or orders its stream after the engine's) before reading."""
+        if reduce not in ("sum", "mean"):
+            raise ValueError(f"reduce must be 'sum' or 'mean', not {reduce!r}")
+        if count is None:
+            count = max(min(self.step_index, self.hist_depth), 1)
+        if first is None:
+            first = (self.step_index - count) % self.hist_depth if self.step_index else 0
+        first, count = int(first), int(count)
+        fid = nat.FIELD[name]
+        if out is not None:
+            import torch
+
+            if reduce != "sum":
+                raise ValueError("a device `out` takes sums only")
+            if not (getattr(out, "is_cuda", False) and out.is_contiguous() and out.dtype == torch.float64
+                    and out.numel() == max(count, 0) * self.n_catch and out.device.index == self.device):
+                raise ValueError(f"out: need a contiguous float64 CUDA tensor of {count} x {self.n_catch} elements "
+                                 f"on cuda:{self.device}")
+            torch.cuda.current_stream(out.device).synchronize()  # `out` may still be in use on torch's stream
+            self._chk(self.lib.tfg_catchment_series(self.h, fid, first, count, ctypes.c_void_p(out.data_ptr()), 1))
+            return out
+        res = np.empty((max(count, 1), self.n_catch), dtype=np.float64)
+        self._chk(self.lib.tfg_catchment_series(self.h, fid, first, count, res.ctypes.data_as(ctypes.c_void_p), 0))
+        if reduce == "mean":
+            cells = self.catchment_cells()
+            res = np.where(cells > 0, res / np.maximum(cells, 1), 0.0)
+        return res
 
 
 

@@ -1,0 +1,58 @@
+"""Per-catchment runoff hydrographs of a gridded run (the
+per-catchment reduction handed to routing).
+
+The reference's driver emits, per catchment and step, the runoff
+``M_total * da_m2`` [m3 s-1] (examples/run_topoflow_glacier.py:112) and
+routes it through a boxcar (:129-131).  On a grid with a catchment-id raster
+the same series is the per-catchment sum of every step's M_total plane.  The
+planes of the last ``hist_depth`` steps are resident in the engine's history,
+so the model advances in blocks of at most ``hist_depth`` steps and each
+block's planes are reduced on the device (GlacierEngine.catchment_series,
+tfg_catchment_series) into the block's rows of one device buffer: no plane
+crosses to the host, no host wait separates the blocks, and the buffer is
+copied out once at the end.
+"""
+
+from __future__ import annotations
+
+import numpy as np
+
+from .routing import boxcar_route
+
+__all__ = ["catchment_hydrographs"]
+
+
+def catchment_hydrographs(eng, nsteps: int, frames=None, group=None, taps: int = 20, on_block=None) -> dict:
+    """Advance `eng` (a GlacierEngine) by nsteps steps and return
+    ``{"runoff": [nsteps][n_catch] m3 s-1, "routed": boxcar_route(runoff, taps)}``.
+
+    frames     forcing frame index per step (default: run()'s step % n_frames)
+    group      torch.distributed group of the row-block shards; when a process
+               group is up the shards' series are summed (one all-reduce) and
+               every rank returns the whole grid's hydrographs
+    on_block   on_block(k0, k1) is called before the block of steps k0..k1-1
+               (relative to this call) is queued: the place to load the forcing
+               frames those steps read
+    """
+    import torch
+
+    nsteps = int(nsteps)
+    if nsteps < 1:
+        raise ValueError("nsteps must be >= 1")
+    if frames is not None and len(frames) != nsteps:
+        raise ValueError("one forcing frame index per step")
+    depth = int(eng.hist_depth)
+    buf = torch.empty((nsteps, int(eng.n_catch)), dtype=torch.float64, device=eng.torch_device)
+    for k0 in range(0, nsteps, depth):
+        k1 = min(k0 + depth, nsteps)
+        if on_block is not None:
+            on_block(k0, k1)
+        first = eng.step_index % depth  # the slot the block's first step writes
+        eng.run(k1 - k0, frames=None if frames is None else frames[k0:k1])
+        eng.catchment_series("M_total", first=first, count=k1 - k0, out=buf[k0:k1])
+    eng.sync()
+    runoff = buf.cpu().numpy() * float(eng.params.da_m2)
+    from .sharding import allreduce_catchment_series
+
+    runoff = allreduce_catchment_series(runoff, group=group)
+    return {"runoff": runoff, "routed": boxcar_route(runoff, taps)}

@@ -20,8 +20,8 @@ from __future__ import annotations
 
 import numpy as np
 
-__all__ = ["row_block", "allreduce_diagnostics", "exchange_halo_rows", "terrain_from_dem_sharded", "ice_flow",
-           "lateral_conduction"]
+__all__ = ["row_block", "allreduce_diagnostics", "allreduce_catchment_series", "exchange_halo_rows",
+           "terrain_from_dem_sharded", "ice_flow", "lateral_conduction"]
 
 
 def row_block(ny_global: int, rank: int, world: int) -> tuple[int, int]:
@@ -52,6 +52,23 @@ def allreduce_diagnostics(diag: np.ndarray, group=None, device=None) -> np.ndarr
     out[:, :5] = sums.cpu().numpy()
     out[:, 5] = maxs.cpu().numpy()
     return out
+
+
+def allreduce_catchment_series(series: np.ndarray, group=None, device=None) -> np.ndarray:
+    """Combine per-shard catchment series (GlacierEngine.catchment_series
+    sums, [nsteps][n_catch], or cell counts): one SUM all-reduce; a copy when
+    no process group is up.  A catchment's mean over shards is the reduced sum
+    over the reduced cell count, never a reduction of the shards' means."""
+    import torch
+    import torch.distributed as dist
+
+    s = np.ascontiguousarray(series, dtype=np.float64)
+    if not (dist.is_available() and dist.is_initialized()):
+        return s.copy()
+    dev = device if device is not None else ("cuda" if dist.get_backend(group) == "nccl" else "cpu")
+    t = torch.from_numpy(s.copy()).to(dev)
+    dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+    return t.cpu().numpy()
 
 
 def exchange_halo_rows(first_row, last_row, group=None):
