@@ -200,6 +200,38 @@ int tfg_set_field(tfg_handle* h, int field, int index, const void* src, int src_
  * (examples/run_topoflow_glacier.py:63-71). */
 int tfg_set_inputs(tfg_handle* h, int frame, const void* src, int src_dtype, int64_t n, int src_on_device);
 
+/* Forcing frames from a per-catchment table, spread over the grid on the
+ * device: for every cell i and each of the frames frame0 .. frame0+nframes-1,
+ * with c = catch_id[i] (0 without a raster) and X_c = table[frame][X][c]
+ * ([nframes][5][n_catch] fp64, the five inputs in tfg_set_inputs order),
+ *   uz = uz_c,  T_air = T_c + lapse_T dz,  P = P_c max(0, 1 + grad_P dz),
+ *   P_air = P_air_c exp(-M g dz / (R (T_c + 273.15)))  when pressure == 1,
+ *   Hum_sp = q_c, capped when rh_max > 0 so that the cell's relative humidity
+ *            (:809-838, the handle's e_sat form) does not exceed rh_max,
+ * where dz = elev[i] - z_ref[c] from the handle's elevation raster.  All
+ * arithmetic is fp64, rounded once to the engine's type.  ds == NULL, or every
+ * term off (0, 0, 0, 0), is a plain gather: each cell gets exactly its
+ * catchment's value; z_ref may then be NULL.  z_ref [n_catch] lives on the
+ * same side as the table.
+ * A host table is copied into the pinned staging ring and the call returns
+ * without waiting for the device; a device table is read in stream order.
+ * TFG_ERR_ARG (no frame is touched): null handle or table, frames outside
+ * 0 .. n_frames, non-finite lapse_T or grad_P, non-finite or negative rh_max,
+ * pressure other than 0 or 1, z_ref == NULL with a term on.  A NaN table entry
+ * reaches only cells of its catchment in its frame.
+ * Replaces: the per-step set_value() calls of a caller
+ * (examples/run_topoflow_glacier.py:63-71), for every cell of every catchment;
+ * the elevation terms have no reference counterpart (one cell per catchment). */
+typedef struct tfg_downscale {
+  double lapse_T;    /* air-temperature lapse rate [degC m-1], e.g. -0.0065     */
+  double grad_P;     /* relative precipitation gradient [m-1]                   */
+  double rh_max;     /* relative-humidity cap (1 = saturation); 0: no cap       */
+  int32_t pressure;  /* 1: barometric correction of P_air                       */
+  int32_t pad;
+} tfg_downscale;
+int tfg_set_catchment_forcing(tfg_handle* h, int frame0, int nframes, const double* table, int table_on_device,
+                              const double* z_ref, const tfg_downscale* ds);
+
 /* The eight BMI outputs in _output_vars order (:28-37): h_snow, h_swe, SM,
  * h_ice, h_iwe, IM, M_total, RH, as dst[8][n], from output-history slot
  * `hist` (h_swe/h_iwe: the current state).  One gather and one copy.

@@ -24,6 +24,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <atomic>
 #include <chrono>
 #include <cstring>
@@ -496,6 +497,7 @@ __global__ void k_terrain(const R* __restrict__ elev, const double* __restrict__
 
 #include "tfg_flow.hpp"  // the optional ice-flow kernels (tfg_ice_flow_*)
 #include "tfg_series.hpp"  // per-catchment sums of history planes (tfg_catchment_series)
+#include "tfg_forcing.hpp"  // per-catchment forcing spread over the grid (tfg_set_catchment_forcing)
 
 // tfg_set_inputs / tfg_get_outputs: the per-step BMI traffic of one call each.
 // src [5][n]: P_air, Hum_sp, P, T_air, uz (BMI order) -> frame planes.
@@ -766,6 +768,15 @@ int ensure_staging(tfg_handle* h, size_t bytes) {
   HIPCHK(h, hipMalloc(&h->staging, bytes));
   h->staging_bytes = bytes;
   return TFG_OK;
+}
+
+// k_forcing_expand's cells per lane: 16-byte stores (4 float / 2 double cells),
+// or with TFG_FORCING_CELLS=1 in the environment one cell per lane -- the
+// form it was measured against (tests/diagnostics/catchment_forcing_timing.py;
+// read at every call, so one process can time both)
+bool forcing_wide() {
+  const char* e = std::getenv("TFG_FORCING_CELLS");
+  return !(e && e[0] == '1' && e[1] == 0);
 }
 
 int grid_for(int64_t n) { return (int)std::min<int64_t>(std::max<int64_t>((n + 255) / 256, 1), 8192); }
@@ -1084,7 +1095,7 @@ int tfg_abi_version(void) { return TFG_ABI_VERSION; }
 #if !defined(__HIP_DEVICE_COMPILE__)
 __attribute__((used)) static const char tfg_build_tag[] =
     "libtfg abi=" TFG_STR(TFG_ABI_VERSION) " arch=gfx950 (hipcc) tfg-src-sha256=" TFG_SRC_HASH
-    "; kernels: k_fused<float|double,exact|fast,...>, k_cell, k_cell_run, k_cell_many, k_diag_reduce, k_catch_series, k_fill_synthetic";
+    "; kernels: k_fused<float|double,exact|fast,...>, k_cell, k_cell_run, k_cell_many, k_diag_reduce, k_catch_series, k_forcing_expand, k_fill_synthetic";
 
 const char* tfg_build_info(void) { return tfg_build_tag; }
 #else
@@ -1964,6 +1975,97 @@ int tfg_set_inputs(tfg_handle* h, int frame, const void* src, int src_dtype, int
     }
   }
   if (int rc = launch_scatter(h, frame, dsrc, src_dtype, n)) return rc;
+  if (b >= 0) HIPCHK(h, hipEventRecord(h->in_ev[b], h->stream));
+  return TFG_OK;
+}
+
+int tfg_set_catchment_forcing(tfg_handle* h, int frame0, int nframes, const double* table, int table_on_device,
+                              const double* z_ref, const tfg_downscale* ds) {
+  if (int rc_ = api_sync(h)) return rc_;  // after a split launch's second part
+  if (!h) return fail(nullptr, TFG_ERR_ARG, "null handle");
+  if (!table) return fail(h, TFG_ERR_ARG, "null table");
+  if (frame0 < 0 || nframes < 1 || (int64_t)frame0 + nframes > h->n_frames)
+    return fail(h, TFG_ERR_ARG, "catchment forcing: frames outside 0..n_frames");
+  bool on = false;
+  if (ds) {
+    if (!std::isfinite(ds->lapse_T) || !std::isfinite(ds->grad_P))
+      return fail(h, TFG_ERR_ARG, "catchment forcing: lapse_T and grad_P must be finite");
+    if (!std::isfinite(ds->rh_max) || ds->rh_max < 0.0)
+      return fail(h, TFG_ERR_ARG, "catchment forcing: rh_max must be finite and >= 0");
+    if (ds->pressure != 0 && ds->pressure != 1) return fail(h, TFG_ERR_ARG, "catchment forcing: pressure must be 0 or 1");
+    on = ds->lapse_T != 0.0 || ds->grad_P != 0.0 || ds->rh_max > 0.0 || ds->pressure == 1;
+  }
+  if (on && !z_ref) return fail(h, TFG_ERR_ARG, "catchment forcing: a downscaling term needs z_ref");
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t frame_len = (size_t)5 * h->n_catch;  // table entries per frame
+  const double* dtab = table;
+  const double* dz = on ? z_ref : nullptr;
+  int b = -1;
+  if (!table_on_device) {
+    // borrowed for this call only, like tfg_set_inputs' src: table | z_ref into a
+    // pinned slot whose previous transfer has completed, then one queued copy
+    const size_t tbytes = (size_t)nframes * frame_len * 8, bytes = tbytes + (on ? (size_t)h->n_catch * 8 : 0);
+    b = h->in_next;
+    h->in_next ^= 1;
+    if (h->in_ev[b]) HIPCHK(h, hipEventSynchronize(h->in_ev[b]));
+    else HIPCHK(h, hipEventCreateWithFlags(&h->in_ev[b], hipEventDisableTiming));
+    if (h->in_cap[b] < bytes) {
+      if (h->in_h[b]) HIPCHK(h, hipHostFree(h->in_h[b]));
+      if (h->in_d[b]) HIPCHK(h, hipFree(h->in_d[b]));
+      h->in_h[b] = h->in_d[b] = nullptr;
+      h->in_cap[b] = 0;
+      HIPCHK(h, hipHostMalloc(&h->in_h[b], bytes, hipHostMallocDefault));
+      HIPCHK(h, hipMalloc(&h->in_d[b], bytes));
+      h->in_cap[b] = bytes;
+    }
+    std::memcpy(h->in_h[b], table, tbytes);
+    if (on) std::memcpy(static_cast<char*>(h->in_h[b]) + tbytes, z_ref, (size_t)h->n_catch * 8);
+    HIPCHK(h, hipMemcpyAsync(h->in_d[b], h->in_h[b], bytes, hipMemcpyHostToDevice, h->stream));
+    dtab = static_cast<const double*>(h->in_d[b]);
+    if (on) dz = dtab + (size_t)nframes * frame_len;
+  }
+  if (h->engine == TFG_F32) {
+    // finite-data tracking: a plain gather of a host table leaves in a plane
+    // exactly its table row's values (every cell is written), so the row
+    // decides; a device table or a downscaled plane is checked lazily
+    static const int map[5] = {F_PA, F_Q, F_P, F_T, F_UZ};  // table order -> frame planes
+    for (int j = 0; j < nframes; ++j)
+      for (int f = 0; f < 5; ++f)
+        h->plane_state[(size_t)(frame0 + j) * kNumForc + map[f]] =
+            (table_on_device || on) ? kUnknown : host_finite_as_f32(table + (size_t)j * frame_len + (size_t)f * h->n_catch, h->n_catch);
+  }
+  ForcingDs d{};
+  if (on) {
+    d.lapse_T = ds->lapse_T;
+    d.grad_P = ds->grad_P;
+    d.rh_max = ds->rh_max;
+    d.pressure = ds->pressure;
+  }
+  d.negM_g_R = h->dp.negM_g_R;
+  d.eps = h->dp.eps;
+  d.one_minus_eps = h->dp.one_minus_eps;
+  d.satterlund = h->dp.satterlund;
+  const bool wide = forcing_wide();
+  for (int j0 = 0; j0 < nframes; j0 += kForcingBatch) {
+    const int nb = std::min(kForcingBatch, nframes - j0);
+    char* fr = static_cast<char*>(h->forc) + (size_t)(frame0 + j0) * kNumForc * h->n_pad * h->rsz;
+    const double* tb = dtab + (size_t)j0 * frame_len;
+    auto launch = [&](auto kern, auto* frp, int v) {
+      using RP = std::remove_pointer_t<decltype(frp)>;
+      hipLaunchKernelGGL(kern, forcing_blocks(h->n, v), kBlock, 0, h->stream, frp, h->n_pad, nb, tb, dz,
+                         static_cast<const RP*>(h->stat), h->catch_id, h->n, h->n_catch, d);
+    };
+    if (h->engine == TFG_F32) {
+      float* p = reinterpret_cast<float*>(fr);
+      if (wide) { if (on) launch(k_forcing_expand<float, true, 4>, p, 4); else launch(k_forcing_expand<float, false, 4>, p, 4); }
+      else { if (on) launch(k_forcing_expand<float, true, 1>, p, 1); else launch(k_forcing_expand<float, false, 1>, p, 1); }
+    } else {
+      double* p = reinterpret_cast<double*>(fr);
+      if (wide) { if (on) launch(k_forcing_expand<double, true, 2>, p, 2); else launch(k_forcing_expand<double, false, 2>, p, 2); }
+      else { if (on) launch(k_forcing_expand<double, true, 1>, p, 1); else launch(k_forcing_expand<double, false, 1>, p, 1); }
+    }
+    HIPCHK(h, hipGetLastError());
+  }
   if (b >= 0) HIPCHK(h, hipEventRecord(h->in_ev[b], h->stream));
   return TFG_OK;
 }

@@ -54,6 +54,12 @@ class TfgParams(ctypes.Structure):
     )] + [("satterlund", ctypes.c_int32), ("ring_len", ctypes.c_int32), ("glens_A", ctypes.c_double)]
 
 
+class TfgDownscale(ctypes.Structure):
+    """tfg_downscale: the elevation terms of tfg_set_catchment_forcing."""
+    _fields_ = [("lapse_T", ctypes.c_double), ("grad_P", ctypes.c_double), ("rh_max", ctypes.c_double),
+                ("pressure", ctypes.c_int32), ("pad", ctypes.c_int32)]
+
+
 # tfg_uniforms, one record per time step (numpy structured dtype, C layout)
 _U_D = ["th", "omega_th", "cos_wth", "sin_wth", "sin_d", "cos_d", "tan_d", "isc_e0", "m_opt",
         "k_et_flat", "flat_sr", "flat_ss"]
@@ -117,6 +123,7 @@ def load() -> ctypes.CDLL:
         "tfg_ice_flow_step": ([vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, dp, dp, i32, i32], i32),
         "tfg_ice_flow_run": ([vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, i32], i32),
         "tfg_set_inputs": ([vp, i32, vp, i32, i64, i32], i32),
+        "tfg_set_catchment_forcing": ([vp, i32, i32, vp, i32, vp, ctypes.POINTER(TfgDownscale)], i32),
         "tfg_get_outputs": ([vp, i32, vp, i32, i64, i32], i32),
         "tfg_update": ([vp, i32, vp, i32, vp, vp, i32, i64], i32),
         "tfg_update_many": ([vp, i32, vp, vp, vp], i32),
@@ -299,5 +306,5 @@ def exported_symbols() -> list[str]:
         "tfg_fill_synthetic", "tfg_last_error", "tfg_terrain_from_dem", "tfg_ice_flow_edges", "tfg_ice_flow_dmax", "tfg_ice_flow_step", "tfg_ice_flow_run", "tfg_set_inputs", "tfg_get_outputs",
         "tfg_update", "tfg_update_many", "tfg_conduction_edges", "tfg_conduction_update", "tfg_conduction_off",
         "tfg_nan_safe_launches", "tfg_set_step_form", "tfg_set_flux", "tfg_set_split", "tfg_join", "tfg_get_split",
-        "tfg_selftest_powers", "tfg_catchment_series",
+        "tfg_selftest_powers", "tfg_catchment_series", "tfg_set_catchment_forcing",
     ) if hasattr(L, n)]

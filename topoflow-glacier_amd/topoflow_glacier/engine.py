@@ -106,6 +106,8 @@ class GlacierEngine:
             t = values.contiguous()
             if name == "catch_id":
                 self._catch_cells = None  # catchment_cells() counts the new raster
+            if name in ("catch_id", "elev"):
+                self._catch_elev = None  # catchment_mean_elevation() sums the new raster
             code = {4: nat.F32, 8: nat.F64}[t.element_size()] if name != "catch_id" else nat.I32
             if t.numel() != self.n:
                 raise ValueError(f"{name}: {t.numel()} values for {self.n} cells")
@@ -115,6 +117,8 @@ class GlacierEngine:
             self._chk(self.lib.tfg_set_field(self.h, fid, index, ctypes.c_void_p(t.data_ptr()), code, self.n, 1))
             self.sync()
             return
+        if name in ("catch_id", "elev"):
+            self._catch_elev = None  # catchment_mean_elevation() sums the new raster
         if name == "catch_id":
             self._catch_cells = None  # catchment_cells() counts the new raster
             a = np.ascontiguousarray(np.broadcast_to(np.asarray(values, dtype=np.int32), (self.n,)))
@@ -220,6 +224,82 @@ class GlacierEngine:
             raise ValueError(f"inputs must be [5][{self.n}]")
         self._chk(self.lib.tfg_set_inputs(self.h, int(index), a.ctypes.data_as(ctypes.c_void_p), nat.F64, self.n, 0))
 
+    def set_catchment_forcing(self, table, frame0: int = 0, z_ref=None, downscale=None) -> None:
+        """Forcing frames frame0 .. frame0+nframes-1 from a per-catchment table
+        [nframes][5][n_catch] (tfg_set_inputs order P_air, Hum_sp, P, T_air, uz;
+        forcing.catchment_table), spread over the grid on the device
+        (tfg_set_catchment_forcing): each cell takes its catchment's values,
+        with the elevation terms of `downscale` (a forcing.Downscale; None or
+        all-off: a plain gather) applied to the cell's height above
+        z_ref [n_catch] (catchment_mean_elevation, allreduce_catchment_elevation).
+
+        `table` (and z_ref) is a host array, or a contiguous float64 torch CUDA
+        tensor on the engine's device, read asynchronously on the engine's
+        stream under set_inputs' stream rules (torch's current stream is
+        drained first when it is not the engine's; the read is recorded with
+        Tensor.record_stream)."""
+        ds = None
+        if downscale is not None:
+            ds = nat.TfgDownscale(float(downscale.lapse_T), float(downscale.grad_P), float(downscale.rh_max),
+                                  int(downscale.pressure), 0)
+        dsp = ctypes.byref(ds) if ds is not None else None
+        if getattr(table, "is_cuda", False):
+            import torch
+
+            tensors = [table] + ([z_ref] if z_ref is not None else [])
+            if table.dim() != 3 or tuple(table.shape[1:]) != (5, self.n_catch):
+                raise ValueError(f"table must be [nframes][5][{self.n_catch}]")
+            if z_ref is not None and not (getattr(z_ref, "is_cuda", False) and z_ref.numel() == self.n_catch):
+                raise ValueError(f"z_ref must be a CUDA tensor of {self.n_catch} elements, like the table")
+            for t in tensors:
+                if t.device.index != self.device:
+                    raise ValueError(f"table on {t.device}, the engine runs on cuda:{self.device}")
+                if t.dtype != torch.float64 or not t.is_contiguous():
+                    raise ValueError("table and z_ref must be contiguous float64 tensors")
+            own = getattr(self, "_stream_ptr", None)
+            cur = torch.cuda.current_stream(table.device)
+            if own is None or own != cur.cuda_stream:
+                cur.synchronize()
+            zp = ctypes.c_void_p(z_ref.data_ptr()) if z_ref is not None else None
+            self._chk(self.lib.tfg_set_catchment_forcing(self.h, int(frame0), int(table.shape[0]),
+                                                         ctypes.c_void_p(table.data_ptr()), 1, zp, dsp))
+            ptr = own or self.stream()
+            if getattr(self, "_ext_stream", (None, None))[0] != ptr:
+                self._ext_stream = (ptr, torch.cuda.ExternalStream(ptr, device=table.device))
+            for t in tensors:
+                t.record_stream(self._ext_stream[1])
+            return
+        a = np.ascontiguousarray(table, dtype=np.float64)
+        if a.ndim != 3 or a.shape[1:] != (5, self.n_catch):
+            raise ValueError(f"table must be [nframes][5][{self.n_catch}]")
+        zp = None
+        if z_ref is not None:
+            z = np.ascontiguousarray(z_ref, dtype=np.float64)
+            if z.shape != (self.n_catch,):
+                raise ValueError(f"z_ref must be [{self.n_catch}]")
+            zp = z.ctypes.data_as(ctypes.c_void_p)
+        self._chk(self.lib.tfg_set_catchment_forcing(self.h, int(frame0), int(a.shape[0]),
+                                                     a.ctypes.data_as(ctypes.c_void_p), 0, zp, dsp))
+
+    def catchment_mean_elevation(self):
+        """(sum [n_catch], cells [n_catch]) of this shard: per catchment, the
+        sum of the elevation raster as the engine holds it (fp32-rounded in
+        the fp32 engine) and the cell count; sum / cells is the catchment's
+        mean elevation, the z_ref of set_catchment_forcing
+        (sharding.allreduce_catchment_elevation for row-block shards).
+        Computed once on the host and cached until catch_id or elev is set."""
+        if getattr(self, "_catch_elev", None) is None:
+            cells = self.catchment_cells()
+            elev = self.get_field("elev")
+            try:
+                cid = self.get_field("catch_id")
+            except nat.NativeError as e:
+                if e.code != nat.ERR_STATE:  # ERR_STATE: no catchment-id raster set
+                    raise
+                cid = np.zeros(self.n, dtype=np.int32)
+            self._catch_elev = (np.bincount(cid, weights=elev, minlength=self.n_catch), cells.astype(np.float64))
+        return self._catch_elev
+
     def get_outputs(self, index: int | None = None, out: np.ndarray | None = None) -> np.ndarray:
         """The eight BMI outputs [8][n] (h_snow, h_swe, SM, h_ice, h_iwe, IM,
         M_total, RH) of history slot `index` (default: the newest) in one call."""
@@ -248,6 +328,7 @@ class GlacierEngine:
         self._chk(self.lib.tfg_fill_synthetic(self.h, int(seed), self.row0, int(nx_global or self.nx),
                                               d.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), self.n_frames))
         self.step_index = 0
+        self._catch_elev = None  # the generator writes the elevation raster
 
     # -- time stepping ------------------------------------------------------------
     _UBLOCK = 512  # steps of uniforms computed at once for short runs

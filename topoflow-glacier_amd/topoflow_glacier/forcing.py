@@ -27,7 +27,8 @@ from pathlib import Path
 
 import numpy as np
 
-__all__ = ["BMI_INPUTS", "INTERNAL", "K_TO_C", "ForcingTable", "read_forcing_csv", "frames_from_table"]
+__all__ = ["BMI_INPUTS", "INTERNAL", "K_TO_C", "ForcingTable", "read_forcing_csv", "frames_from_table",
+           "INPUT_ORDER", "Downscale", "catchment_table"]
 
 K_TO_C = -273.15  # BmiTopoflowGlacier.K_to_C (bmi_topoflow_glacier.py:290)
 
@@ -95,3 +96,50 @@ def read_forcing_csv(path: str | Path, start_time: str | None = None, end_time: 
 def frames_from_table(table: ForcingTable, ncell: int = 1) -> dict:
     """internal name -> [nsteps][ncell] frames (the table broadcast to ncell cells)."""
     return {k: np.ascontiguousarray(np.broadcast_to(v[:, None], (len(v), ncell))) for k, v in table.inputs.items()}
+
+
+INPUT_ORDER = ("P_air", "Hum_sp", "P", "T_air", "uz")  # tfg_set_inputs order: the five inputs the physics reads
+
+
+@dataclass
+class Downscale:
+    """Elevation terms of GlacierEngine.set_catchment_forcing (tfg_downscale),
+    every one off by default.  With dz = a cell's elevation minus its
+    catchment's reference elevation:
+
+      lapse_T   T_air = T_c + lapse_T dz                       [degC m-1], e.g. -0.0065
+      grad_P    P = P_c max(0, 1 + grad_P dz)                  [m-1]
+      pressure  1: P_air = P_air_c exp(-M g dz / (R (T_c + 273.15)))
+      rh_max    > 0: Hum_sp capped so that the cell's relative humidity stays
+                at or under rh_max (1.0 = saturation)
+    """
+
+    lapse_T: float = 0.0
+    grad_P: float = 0.0
+    pressure: int = 0
+    rh_max: float = 0.0
+
+    @property
+    def on(self) -> bool:
+        return bool(self.lapse_T != 0.0 or self.grad_P != 0.0 or self.pressure == 1 or self.rh_max > 0.0)
+
+
+def catchment_table(tables) -> np.ndarray:
+    """[nsteps][5][n_catch] float64 in tfg_set_inputs order (P_air, Hum_sp, P,
+    T_air, uz) from one ForcingTable per catchment, in catchment-id order: what
+    GlacierEngine.set_catchment_forcing spreads over the grid.  The tables
+    must cover the same steps: equal lengths and equal times."""
+    tables = list(tables)
+    if not tables:
+        raise ValueError("catchment_table: no tables")
+    n = len(tables[0])
+    for c, t in enumerate(tables):
+        if len(t) != n:
+            raise ValueError(f"catchment_table: catchment {c} has {len(t)} steps, catchment 0 has {n}")
+        if not np.array_equal(np.asarray(t.times), np.asarray(tables[0].times)):
+            raise ValueError(f"catchment_table: the times of catchment {c} differ from catchment 0's")
+    out = np.empty((n, 5, len(tables)), dtype=np.float64)
+    for c, t in enumerate(tables):
+        for v, name in enumerate(INPUT_ORDER):
+            out[:, v, c] = t.inputs[name]
+    return out

@@ -19,7 +19,7 @@ import numpy as np
 
 from .routing import boxcar_route
 
-__all__ = ["catchment_hydrographs"]
+__all__ = ["catchment_hydrographs", "forced_catchment_hydrographs"]
 
 
 def catchment_hydrographs(eng, nsteps: int, frames=None, group=None, taps: int = 20, on_block=None) -> dict:
@@ -56,3 +56,44 @@ def catchment_hydrographs(eng, nsteps: int, frames=None, group=None, taps: int =
 
     runoff = allreduce_catchment_series(runoff, group=group)
     return {"runoff": runoff, "routed": boxcar_route(runoff, taps)}
+
+
+def forced_catchment_hydrographs(eng, table, z_ref=None, downscale=None, group=None, taps: int = 20) -> dict:
+    """catchment_hydrographs driven by a per-catchment forcing table
+    [nsteps][5][n_catch] (forcing.catchment_table; a host array or a float64
+    CUDA tensor): before each block of steps is queued, the block's frames are
+    produced on the device from its table rows
+    (GlacierEngine.set_catchment_forcing), step k of this call into frame
+    k % n_frames, which the step is then told to read.  A block that wraps
+    the frame ring takes two calls.  The block before it has been queued by
+    then, and the engine's stream keeps the order, so no frame is overwritten
+    before the step that reads it; that needs n_frames >= hist_depth (a block
+    is at most hist_depth steps).
+
+    downscale  a forcing.Downscale; None or all-off spreads the values as they are
+    z_ref      [n_catch] reference elevations; by default, when a term is on,
+               the catchments' mean elevations over all shards
+               (GlacierEngine.catchment_mean_elevation,
+               sharding.allreduce_catchment_elevation)
+    """
+    nsteps, nf = int(table.shape[0]), int(eng.n_frames)
+    if nf < int(eng.hist_depth):
+        raise ValueError(f"n_frames ({nf}) must be >= hist_depth ({eng.hist_depth}): a block's frames are resident together")
+    if z_ref is None and downscale is not None and downscale.on:
+        from .sharding import allreduce_catchment_elevation
+
+        z_ref = allreduce_catchment_elevation(*eng.catchment_mean_elevation(), group=group)
+        if getattr(table, "is_cuda", False):
+            import torch
+
+            z_ref = torch.from_numpy(z_ref).to(table.device)
+
+    def write_frames(k0, k1):
+        f0 = k0 % nf
+        head = min(k1 - k0, nf - f0)
+        eng.set_catchment_forcing(table[k0:k0 + head], frame0=f0, z_ref=z_ref, downscale=downscale)
+        if k0 + head < k1:  # the block wraps the frame ring
+            eng.set_catchment_forcing(table[k0 + head:k1], frame0=0, z_ref=z_ref, downscale=downscale)
+
+    frames = (np.arange(nsteps) % nf).astype(np.int32)
+    return catchment_hydrographs(eng, nsteps, frames=frames, group=group, taps=taps, on_block=write_frames)

@@ -20,7 +20,8 @@ from __future__ import annotations
 
 import numpy as np
 
-__all__ = ["row_block", "allreduce_diagnostics", "allreduce_catchment_series", "exchange_halo_rows",
+__all__ = ["row_block", "allreduce_diagnostics", "allreduce_catchment_series", "allreduce_catchment_elevation",
+           "exchange_halo_rows",
            "terrain_from_dem_sharded", "ice_flow", "lateral_conduction"]
 
 
@@ -69,6 +70,18 @@ def allreduce_catchment_series(series: np.ndarray, group=None, device=None) -> n
     t = torch.from_numpy(s.copy()).to(dev)
     dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
     return t.cpu().numpy()
+
+
+def allreduce_catchment_elevation(sum, cells, group=None, device=None) -> np.ndarray:
+    """The global reference elevation z_ref [n_catch] of
+    GlacierEngine.set_catchment_forcing from the shards' per-catchment
+    elevation sums and cell counts (GlacierEngine.catchment_mean_elevation):
+    both are summed over the shards in one all-reduce, then divided.  A
+    catchment without cells anywhere gets 0.  Without a process group: this
+    shard's means."""
+    both = allreduce_catchment_series(np.stack([np.asarray(sum, dtype=np.float64), np.asarray(cells, dtype=np.float64)]),
+                                      group=group, device=device)
+    return np.where(both[1] > 0, both[0] / np.maximum(both[1], 1.0), 0.0)
 
 
 def exchange_halo_rows(first_row, last_row, group=None):
