@@ -626,6 +626,8 @@ struct tfg_handle {
   double* series_out = nullptr;  // [hist_depth][n_catch]
   float* d_diurnal = nullptr;
   int32_t* d_flag = nullptr;
+  // tfg_step's staged steps: [nsteps] tfg_uniforms, then the [nsteps] StepAddr
+  // records of the same steps (step_table, stage_bytes); d_u2 and h_u[] alike
   tfg_uniforms* d_u = nullptr;
   int64_t d_u_cap = 0;
   tfg_uniforms* h_u[2] = {nullptr, nullptr};
@@ -1015,8 +1017,8 @@ struct Part {
 };
 
 template <class R, bool EXACT>
-int launch_fused(tfg_handle* h, const tfg_uniforms* d_u, int K, int blocks, size_t lds, const IoArgs& io, bool ns,
-                 const Part* part = nullptr) {
+int launch_fused(tfg_handle* h, const tfg_uniforms* d_u, const StepAddr* d_t, int K, int blocks, size_t lds,
+                 const IoArgs& io, bool ns, const Part* part = nullptr) {
   const hipStream_t stream = part ? part->stream : h->stream;
   KArgs a;
   a.p = h->dp;
@@ -1034,7 +1036,7 @@ int launch_fused(tfg_handle* h, const tfg_uniforms* d_u, int K, int blocks, size
   const int64_t c0 = part ? part->c0 : 0;
   a.part_c0 = c0;
   const size_t rb = (size_t)c0 * h->rsz;
-  const FusedBufs fb = {d_u, static_cast<const char*>(h->forc) + rb, static_cast<const char*>(h->stat) + rb, h->geo + c0,
+  const FusedBufs fb = {d_u, d_t, static_cast<const char*>(h->forc) + rb, static_cast<const char*>(h->stat) + rb, h->geo + c0,
                         h->catch_id ? h->catch_id + c0 : nullptr, h->st + c0, h->tot + c0, h->ring + c0,
                         static_cast<char*>(h->hist) + rb, h->slab + (part ? part->slab_row0 : 0) * h->n_catch * 6,
                         h->qc ? static_cast<const char*>(h->qc) + rb : nullptr};
@@ -1044,37 +1046,23 @@ int launch_fused(tfg_handle* h, const tfg_uniforms* d_u, int K, int blocks, size
     HIPCHK(h, launch_fused_exact(a, fb, rd, ct, h->qc_on, blocks, lds, stream));
     return TFG_OK;
   } else {
-  if (h->flux_f64) {  // the fp64-flux form's instantiations live in tfg_fused_prec.hip
-    HIPCHK(h, launch_fused_prec(a, fb, rd, ct, h->qc_on, ns, blocks, lds, stream));
+    // the form's instantiations live in its own unit (tfg_fused.hpp, launch_fused_fast)
+    const bool sat = h->dp.satterlund != 0;
+    hipError_t e;
+    if (h->flux_f64) e = sat ? launch_fused_fast<true, true>(a, fb, rd, ct, h->qc_on, ns, blocks, lds, stream)
+                             : launch_fused_fast<true, false>(a, fb, rd, ct, h->qc_on, ns, blocks, lds, stream);
+    else e = sat ? launch_fused_fast<false, true>(a, fb, rd, ct, h->qc_on, ns, blocks, lds, stream)
+                 : launch_fused_fast<false, false>(a, fb, rd, ct, h->qc_on, ns, blocks, lds, stream);
+    HIPCHK(h, e);
     return TFG_OK;
-  }
-  constexpr int C = kCellsPerThread;
-#define TFG_ARGS a, d_u, (const R*)fb.forc, (const R*)fb.stat, fb.geo, fb.catch_id, fb.st, fb.tot, fb.ring, (R*)fb.hist, \
-                 fb.slab, (const R*)fb.qc
-#define TFG_LAUNCH(RD, CT, QC, NS) \
-  hipLaunchKernelGGL((k_fused<R, EXACT, RD, CT, QC, C, NS>), blocks, kBlock, lds, stream, TFG_ARGS)
-#define TFG_LAUNCH_NS(RD, CT, QC) \
-  do { if (ns) TFG_LAUNCH(RD, CT, QC, true); else TFG_LAUNCH(RD, CT, QC, false); } while (0)
-  if (h->qc_on) {  // the optional lateral conduction term (tfg_conduction_update / TFG_ST_QC)
-    if (rd && ct) TFG_LAUNCH_NS(true, true, true);
-    else if (rd) TFG_LAUNCH_NS(true, false, true);
-    else if (ct) TFG_LAUNCH_NS(false, true, true);
-    else TFG_LAUNCH_NS(false, false, true);
-  } else {
-    if (rd && ct) TFG_LAUNCH_NS(true, true, false);
-    else if (rd) TFG_LAUNCH_NS(true, false, false);
-    else if (ct) TFG_LAUNCH_NS(false, true, false);
-    else TFG_LAUNCH_NS(false, false, false);
-  }
-#undef TFG_LAUNCH_NS
-#undef TFG_LAUNCH
-#undef TFG_ARGS
-  HIPCHK(h, hipGetLastError());
-  return TFG_OK;
   }
 }
 
 }  // namespace
+
+// the default form of the fp32 engine's k_fused (Brutsaert, fp32 fluxes) is compiled in this unit
+template hipError_t tfg_kern::launch_fused_fast<false, false>(const KArgs&, const FusedBufs&, bool, bool, bool, bool, int,
+                                                              size_t, hipStream_t);
 
 // ===========================================================================
 // C ABI
@@ -1667,8 +1655,28 @@ int choose_form(tfg_handle* h, const tfg_uniforms* u, int K, const IoArgs& io, b
   return TFG_OK;
 }
 
-int launch_steps(tfg_handle* h, const tfg_uniforms* d_u, const tfg_uniforms* u, int64_t nsteps,
-                 const IoArgs& io = IoArgs(), bool split = false) {
+// The step table of u[0 .. nsteps) (tfg_fused.hpp, StepAddr): byte offsets in
+// the handle's engine type and plane stride.  check_step has held every index
+// to its buffer.  tfg_update's step (io) reads its forcing at the host block
+// itself: a zero offset.
+void step_table(const tfg_handle* h, const tfg_uniforms* u, int64_t nsteps, StepAddr* t, bool io = false) {
+  const int64_t plane = h->n_pad * (int64_t)h->rsz;
+  for (int64_t k = 0; k < nsteps; ++k)
+    t[k] = {io ? 0 : u[k].frame * kNumForc * plane, u[k].slot * h->n_pad * (int64_t)sizeof(int32_t),
+            u[k].hist * kNumHist * plane, 0};
+}
+// Bytes of nsteps staged steps: the uniforms, then their table.  A launch of K
+// steps from k0 reads records k0 .. k0 + K - 1 only (k_fused clamps its
+// read-ahead to the launch's last record, it does not repeat trailing records),
+// and k0 + K <= nsteps: no read passes the table's end.
+constexpr size_t stage_bytes(int64_t nsteps) { return (size_t)nsteps * (sizeof(tfg_uniforms) + sizeof(StepAddr)); }
+static_assert(sizeof(tfg_uniforms) % alignof(StepAddr) == 0 && sizeof(tfg_uniforms) % 32 == 0,
+              "the table after the uniforms keeps its records aligned");
+const StepAddr* table_of(const tfg_uniforms* d_u, int64_t nsteps) { return reinterpret_cast<const StepAddr*>(d_u + nsteps); }
+
+// d_t (the side stream's copy: d_t2) is the step table of the records at d_u.
+int launch_steps(tfg_handle* h, const tfg_uniforms* d_u, const StepAddr* d_t, const StepAddr* d_t2, const tfg_uniforms* u,
+                 int64_t nsteps, const IoArgs& io = IoArgs(), bool split = false) {
   if (int rc = prepare_steps(h)) return rc;
   const int blocks = fused_blocks(h);
   const size_t lds = (size_t)kWaves * h->n_catch * 6 * sizeof(double);
@@ -1712,8 +1720,8 @@ int launch_steps(tfg_handle* h, const tfg_uniforms* d_u, const tfg_uniforms* u, 
       const int bB = (int)(fit ? chB : std::min<int64_t>(chB, h->max_blocks / 2));
       const Part pa = {0, nA, std::min(h->n, nA), 0, h->stream};
       const Part pb = {nA, h->n_pad - nA, std::max<int64_t>(h->n - nA, 0), bA, h->side};
-      if ((rc = launch_fused<float, false>(h, d_u + k0, K, bA, lds, io, ns, &pa))) return rc;
-      if ((rc = launch_fused<float, false>(h, h->d_u2 + k0, K, bB, lds, io, ns, &pb))) return rc;
+      if ((rc = launch_fused<float, false>(h, d_u + k0, d_t + k0, K, bA, lds, io, ns, &pa))) return rc;
+      if ((rc = launch_fused<float, false>(h, h->d_u2 + k0, d_t2 + k0, K, bB, lds, io, ns, &pb))) return rc;
       h->side_busy = true;
       if (ns) {
         ++h->ns_launches;
@@ -1722,14 +1730,14 @@ int launch_steps(tfg_handle* h, const tfg_uniforms* d_u, const tfg_uniforms* u, 
     } else if (h->engine == TFG_F32) {
       bool ns = true;
       if ((rc = choose_form(h, u + k0, K, io, &ns))) return rc;
-      rc = launch_fused<float, false>(h, d_u + k0, K, blocks, lds, io, ns);
+      rc = launch_fused<float, false>(h, d_u + k0, d_t + k0, K, blocks, lds, io, ns);
       if (ns) {
         ++h->ns_launches;
         // the NaN-safe form may have carried missing data into the state
         if (h->state_state == kOk) h->state_state = kUnknown;
       }
     } else {
-      rc = launch_fused<double, true>(h, d_u + k0, K, blocks, lds, io, false);
+      rc = launch_fused<double, true>(h, d_u + k0, d_t + k0, K, blocks, lds, io, false);
     }
     if (rc) return rc;
     h->depths_derived = true;
@@ -1760,7 +1768,7 @@ int tfg_step(tfg_handle* h, const tfg_uniforms* u, int64_t nsteps) {
   if (h->h_u_cap[b] < nsteps) {
     if (h->h_u[b]) HIPCHK(h, hipHostFree(h->h_u[b]));
     h->h_u[b] = nullptr;
-    HIPCHK(h, hipHostMalloc((void**)&h->h_u[b], (size_t)nsteps * sizeof(tfg_uniforms), hipHostMallocDefault));
+    HIPCHK(h, hipHostMalloc((void**)&h->h_u[b], stage_bytes(nsteps), hipHostMallocDefault));
     h->h_u_cap[b] = nsteps;
   }
   if (h->d_u_cap < nsteps) {
@@ -1768,25 +1776,28 @@ int tfg_step(tfg_handle* h, const tfg_uniforms* u, int64_t nsteps) {
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (h->d_u) HIPCHK(h, hipFree(h->d_u));
     h->d_u = nullptr;
-    HIPCHK(h, hipMalloc((void**)&h->d_u, (size_t)nsteps * sizeof(tfg_uniforms)));
+    HIPCHK(h, hipMalloc((void**)&h->d_u, stage_bytes(nsteps)));
     h->d_u_cap = nsteps;
   }
+  // the uniforms and, right after them, their step table: one copy
   std::memcpy(h->h_u[b], u, (size_t)nsteps * sizeof(tfg_uniforms));
-  HIPCHK(h, hipMemcpyAsync(h->d_u, h->h_u[b], (size_t)nsteps * sizeof(tfg_uniforms), hipMemcpyHostToDevice, h->stream));
+  step_table(h, u, nsteps, reinterpret_cast<StepAddr*>(h->h_u[b] + nsteps));
+  HIPCHK(h, hipMemcpyAsync(h->d_u, h->h_u[b], stage_bytes(nsteps), hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipEventRecord(h->h_u_ev[b], h->stream));
   if (split) {
     if (h->d_u2_cap < nsteps) {
       HIPCHK(h, hipStreamSynchronize(h->side));  // its launches may still read d_u2
       if (h->d_u2) HIPCHK(h, hipFree(h->d_u2));
       h->d_u2 = nullptr;
-      HIPCHK(h, hipMalloc((void**)&h->d_u2, (size_t)nsteps * sizeof(tfg_uniforms)));
+      HIPCHK(h, hipMalloc((void**)&h->d_u2, stage_bytes(nsteps)));
       h->d_u2_cap = nsteps;
     }
     if (!h->h_u_ev2[b]) HIPCHK(h, hipEventCreateWithFlags(&h->h_u_ev2[b], hipEventDisableTiming));
-    HIPCHK(h, hipMemcpyAsync(h->d_u2, h->h_u[b], (size_t)nsteps * sizeof(tfg_uniforms), hipMemcpyHostToDevice, h->side));
+    HIPCHK(h, hipMemcpyAsync(h->d_u2, h->h_u[b], stage_bytes(nsteps), hipMemcpyHostToDevice, h->side));
     HIPCHK(h, hipEventRecord(h->h_u_ev2[b], h->side));
   }
-  return launch_steps(h, h->d_u, u, nsteps, IoArgs(), split);
+  return launch_steps(h, h->d_u, table_of(h->d_u, nsteps), split ? table_of(h->d_u2, nsteps) : nullptr, u, nsteps, IoArgs(),
+                      split);
 }
 
 int tfg_get_diag(tfg_handle* h, double* out, int n_catch) {
@@ -2185,12 +2196,13 @@ int tfg_update(tfg_handle* h, int frame, const void* src, int src_dtype, const t
   if (int rc = check_step(h, u, 1)) return rc;
   if (u->frame != frame) return fail(h, TFG_ERR_ARG, "uniforms: frame differs from the input frame");
   HIPCHK(h, hipSetDevice(h->device));
-  // One pinned block [forcing kNumForc x n_pad (engine type) | uniforms | outputs 8 x n f64];
+  // One pinned block [forcing kNumForc x n_pad (engine type) | uniforms, step record | outputs 8 x n f64];
   // the call is synchronous, so one block suffices.
   const int64_t np = h->n_pad;
   const size_t in_b = (size_t)kNumForc * np * h->rsz;
   const size_t u_off = (in_b + 255) & ~(size_t)255;
   const size_t out_off = u_off + 256;
+  static_assert(stage_bytes(1) <= 256, "the step's uniforms and its table record fit their slot");
   const size_t out_b = (size_t)8 * n * 8;
   const int blocks = fused_blocks(h);
   const size_t flag_off = (out_off + out_b + 255) & ~(size_t)255;
@@ -2263,6 +2275,7 @@ int tfg_update(tfg_handle* h, int frame, const void* src, int src_dtype, const t
     }
   }
   std::memcpy(h->io_h + u_off, u, sizeof(tfg_uniforms));
+  step_table(h, u, 1, reinterpret_cast<StepAddr*>(h->io_h + u_off + sizeof(tfg_uniforms)), true);
   IoArgs io;
   if (h->engine == TFG_F32) {  // finite-data status of the step's inputs, as the kernel reads them
     io.in_state = kOk;
@@ -2275,7 +2288,8 @@ int tfg_update(tfg_handle* h, int frame, const void* src, int src_dtype, const t
   io.out = reinterpret_cast<double*>(h->io_d + out_off);
   io.flag = reinterpret_cast<uint32_t*>(h->io_d + flag_off);
   io.seq = ++h->io_seq == 0 ? ++h->io_seq : h->io_seq;  // never 0, the initial flag value
-  if (int rc = launch_steps(h, reinterpret_cast<const tfg_uniforms*>(h->io_d + u_off), u, 1, io)) return rc;
+  const tfg_uniforms* d_u = reinterpret_cast<const tfg_uniforms*>(h->io_d + u_off);
+  if (int rc = launch_steps(h, d_u, table_of(d_u, 1), nullptr, u, 1, io)) return rc;
   if (h->engine == TFG_F32)  // the kernel stored the inputs into the frame
     std::fill_n(h->plane_state.begin() + (size_t)frame * kNumForc, kNumForc, io.in_state);
   TFG_TSTAMP(t_l1);

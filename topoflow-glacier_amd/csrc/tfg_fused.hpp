@@ -1,8 +1,9 @@
 // tfg_fused.hpp -- the fused multi-step kernel k_fused<R, EXACT, READ_DEPTHS,
-// CATCH, QC, C, NS> and its helpers, shared by the two translation units of the
-// engine library: tfg_engine.hip (the C ABI, every other kernel, and the fp32
-// engine's instantiations) and tfg_fused_f64.hip (the fp64 engine's
-// instantiations, compiled with different code-motion flags; see there).
+// CATCH, QC, C, NS, PREC, SAT> and its helpers, shared by the translation units
+// of the engine library: tfg_engine.hip (the C ABI, every other kernel, and the
+// fp32 engine's default instantiations), tfg_fused_f64.hip (the fp64 engine's
+// instantiations, compiled with different code-motion flags; see there) and the
+// units of the fp32 engine's other forms (launch_fused_fast below lists them).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -61,6 +62,22 @@ struct KArgs {
   int64_t n_step = 0;
   int64_t part_c0 = 0;
 };
+
+// One record of the step table, engine-private, beside each step's
+// tfg_uniforms: the byte offsets of the step's forcing frame, window slot and
+// history slot from the launch's `forc`, `ring` and `hist` kernel parameters
+// (frame * 5 * n_pad * sizeof(R), slot * n_pad * 4, hist * 6 * n_pad *
+// sizeof(R)), written by the host when it stages the uniforms (step_table in
+// tfg_engine.hip).  The step loop then takes a base with one 64-bit add
+// instead of an index load, a wait and a 64-bit product per access.  Offsets,
+// not absolute pointers: the accesses stay based on the __restrict__ kernel
+// parameters (see KArgs).  A part of a split launch uses the same offsets, its
+// first cell being in its buffer arguments already.  tfg_update's launch
+// (KArgs::io_in) has a zero forcing offset: its base is io_in itself.
+struct StepAddr {
+  int64_t forc, ring, hist, pad_;
+};
+static_assert(sizeof(StepAddr) == 32, "one aligned scalar load of four dwords reaches forc and ring");
 
 // TFG_STEP_PARAMS(p): inside a step loop, `p` names the launch's model
 // constants (KArgs::p, at offset 0 of the kernel-argument segment) through a
@@ -180,9 +197,14 @@ constexpr int kMinWavesExact = 2;  // fp64 engine: 256 VGPRs, no scratch spills
 constexpr int kMinWavesPrec = 4;
 // NS (fast engine only): the NaN-safe form of the step (tfg::cell_step_fast),
 // for launches the host could not verify to read only finite values.  PREC
-// (fast engine only): the fp64 flux form (tfg_set_flux(TFG_FLUX_F64)).
-template <class R, bool EXACT, bool READ_DEPTHS, bool CATCH, bool QC, int C, bool NS = false, bool PREC = false>
+// (fast engine only): the fp64 flux form (tfg_set_flux(TFG_FLUX_F64)).  SAT
+// (fast engine only): the Satterlund vapour-pressure form (DevParams::satterlund,
+// a constant of the handle) instead of Brutsaert's, chosen at the launch so the
+// step carries no load, branch or select for it.
+template <class R, bool EXACT, bool READ_DEPTHS, bool CATCH, bool QC, int C, bool NS = false, bool PREC = false,
+          bool SAT = false>
 __global__ __launch_bounds__(kBlock, EXACT ? kMinWavesExact : (PREC ? kMinWavesPrec : kMinWaves)) void k_fused(const KArgs a, const tfg_uniforms* __restrict__ uni,
+                                                  const StepAddr* __restrict__ tab,  // [K] beside uni
                                                   const R* __restrict__ forc,      // [n_frames][5][n_pad]
                                                   const R* __restrict__ stat,      // [3][n_pad]
                                                   const float* __restrict__ geo,   // [kGeoF][n_pad] f32 + [2][n_pad] f64
@@ -342,10 +364,17 @@ __global__ __launch_bounds__(kBlock, EXACT ? kMinWavesExact : (PREC ? kMinWavesP
       // (ring_len == 1) runs unfused (tfg_step): its slot read would otherwise
       // precede the write of the step before.
       struct Frame { R P[C], T[C], Q[C], PA[C], UZ[C]; int32_t q[C]; };
+      // the forcing base of the launch: tfg_update's host block (its record's
+      // forcing offset is zero) or the frames
+      const char* const fbase = a.io_in ? static_cast<const char*>(a.io_in) : reinterpret_cast<const char*>(forc);
+      // Requests k >= K (the read-ahead of the last steps, up to K + 3) are
+      // clamped to the launch's own last record: they re-request its frame and
+      // slot, fetch nothing of a later launch, and never read past tab[K - 1].
       auto fetch = [&](int k, Frame& f) {
-        const tfg_uniforms* un = uni + (k < a.K ? k : a.K - 1);
-        const R* __restrict__ fr =
-            a.io_in ? static_cast<const R*>(a.io_in) : forc + (int64_t)un->frame * kNumForc * n_pad;
+        const StepAddr* ta = tab + (k < a.K ? k : a.K - 1);
+        const int64_t fo = ta->forc, ro = ta->ring;
+        const R* __restrict__ fr = reinterpret_cast<const R*>(fbase + fo);
+        const int32_t* rs = reinterpret_cast<const int32_t*>(reinterpret_cast<const char*>(ring) + ro);
         static_assert(C == 1, "streamed step accesses are per cell");
         static_assert(sizeof(R) == 4 || sizeof(R) == 8, "R is float or double");
         const uint32_t oR = lane_off(lc * (uint32_t)sizeof(R));
@@ -354,7 +383,7 @@ __global__ __launch_bounds__(kBlock, EXACT ? kMinWavesExact : (PREC ? kMinWavesP
         f.Q[0] = sload(fr + F_Q * n_pad, oR);
         f.PA[0] = sload(fr + F_PA * n_pad, oR);
         f.UZ[0] = sload(fr + F_UZ * n_pad, oR);
-        f.q[0] = sload(ring + (int64_t)un->slot * n_pad, sizeof(R) == 4 ? oR : lane_off(lc * 4u));
+        f.q[0] = sload(rs, sizeof(R) == 4 ? oR : lane_off(lc * 4u));
       };
       auto advance = [&](int k, const Frame& f) {
         // SGPR spills 62 -> 56 (fp32) and 170 -> 111 (fp64); same-box A/B:
@@ -377,16 +406,17 @@ __global__ __launch_bounds__(kBlock, EXACT ? kMinWavesExact : (PREC ? kMinWavesP
             o_im[j] = (R)o.IM; o_mt[j] = (R)o.M_total; o_rh[j] = (R)o.RH;
           } else {
             tfg::CellOutF o;
-            tfg::cell_step_fast<QC, NS, PREC>(p, SF[j], up, u, geo_d, n_pad, c0 + j, (float)f.P[j], (float)f.T[j],
-                                        (float)f.Q[j], (float)f.PA[j], (float)f.UZ[j], f.q[j], qn[j], cs[j], o, df[j],
-                                        (float)qc[j]);
+            tfg::cell_step_fast<QC, NS, PREC, SAT>(p, SF[j], up, u, geo_d, n_pad, c0 + j, (float)f.P[j], (float)f.T[j],
+                                                   (float)f.Q[j], (float)f.PA[j], (float)f.UZ[j], f.q[j], qn[j], cs[j],
+                                                   o, df[j], (float)qc[j]);
             o_hs[j] = (R)o.h_snow; o_sm[j] = (R)o.SM; o_hi[j] = (R)o.h_ice;
             o_im[j] = (R)o.IM; o_mt[j] = (R)o.M_total; o_rh[j] = (R)o.RH;
           }
         }
         const uint32_t oR = lane_off(lc * (uint32_t)sizeof(R));
-        sstore(ring + (int64_t)u.slot * n_pad, sizeof(R) == 4 ? oR : lane_off(lc * 4u), qn[0]);
-        R* __restrict__ h = hist + (int64_t)u.hist * kNumHist * n_pad;
+        const int64_t ro = tab[k].ring, ho = tab[k].hist;
+        sstore(reinterpret_cast<int32_t*>(reinterpret_cast<char*>(ring) + ro), sizeof(R) == 4 ? oR : lane_off(lc * 4u), qn[0]);
+        R* __restrict__ h = reinterpret_cast<R*>(reinterpret_cast<char*>(hist) + ho);
         sstore(h + H_HSNOW * n_pad, oR, o_hs[0]);
         sstore(h + H_SM * n_pad, oR, o_sm[0]);
         sstore(h + H_HICE * n_pad, oR, o_hi[0]);
@@ -552,6 +582,7 @@ __global__ __launch_bounds__(kBlock, EXACT ? kMinWavesExact : (PREC ? kMinWavesP
 // The buffers of one k_fused launch (tfg_handle's planes; R = the engine type).
 struct FusedBufs {
   const tfg_uniforms* uni;
+  const StepAddr* tab;
   const void* forc;
   const void* stat;
   const float* geo;
@@ -568,9 +599,47 @@ struct FusedBufs {
 // (read_depths, catchments, qc_on) on `stream`.
 hipError_t launch_fused_exact(const KArgs& a, const FusedBufs& b, bool read_depths, bool catchments, bool qc_on,
                               int blocks, size_t lds, hipStream_t stream);
-// The fp32 engine's fp64-flux form (tfg_fused_prec.hip): the instantiation for
-// (read_depths, catchments, qc_on, nan_safe) on `stream`.
-hipError_t launch_fused_prec(const KArgs& a, const FusedBufs& b, bool read_depths, bool catchments, bool qc_on,
-                             bool nan_safe, int blocks, size_t lds, hipStream_t stream);
+// The fp32 engine's k_fused launch: the instantiation of the form <PREC, SAT>
+// for (read_depths, catchments, qc_on, nan_safe) on `stream`.  Each form's
+// sixteen kernels are compiled in one translation unit, which instantiates this
+// function explicitly, so that the library's units still compile side by side:
+//   <false, false>  tfg_engine.hip          the default and the headline
+//   <true,  false>  tfg_fused_prec.hip      the fp64-flux form
+//   <false, true>   tfg_fused_sat.hip       Satterlund
+//   <true,  true>   tfg_fused_prec_sat.hip  Satterlund, fp64 flux
+template <bool PREC, bool SAT>
+hipError_t launch_fused_fast(const KArgs& a, const FusedBufs& b, bool read_depths, bool catchments, bool qc_on,
+                             bool nan_safe, int blocks, size_t lds, hipStream_t stream) {
+  constexpr int C = kCellsPerThread;
+#define TFG_ARGS a, b.uni, b.tab, static_cast<const float*>(b.forc), static_cast<const float*>(b.stat), b.geo, b.catch_id, \
+                 b.st, b.tot, b.ring, static_cast<float*>(b.hist), b.slab, static_cast<const float*>(b.qc)
+#define TFG_LAUNCH(RD, CT, QC, NS) \
+  hipLaunchKernelGGL((k_fused<float, false, RD, CT, QC, C, NS, PREC, SAT>), blocks, kBlock, lds, stream, TFG_ARGS)
+#define TFG_LAUNCH_NS(RD, CT, QC) \
+  do { if (nan_safe) TFG_LAUNCH(RD, CT, QC, true); else TFG_LAUNCH(RD, CT, QC, false); } while (0)
+  if (qc_on) {  // the optional lateral conduction term (tfg_conduction_update / TFG_ST_QC)
+    if (read_depths && catchments) TFG_LAUNCH_NS(true, true, true);
+    else if (read_depths) TFG_LAUNCH_NS(true, false, true);
+    else if (catchments) TFG_LAUNCH_NS(false, true, true);
+    else TFG_LAUNCH_NS(false, false, true);
+  } else {
+    if (read_depths && catchments) TFG_LAUNCH_NS(true, true, false);
+    else if (read_depths) TFG_LAUNCH_NS(true, false, false);
+    else if (catchments) TFG_LAUNCH_NS(false, true, false);
+    else TFG_LAUNCH_NS(false, false, false);
+  }
+#undef TFG_LAUNCH_NS
+#undef TFG_LAUNCH
+#undef TFG_ARGS
+  return hipGetLastError();
+}
+extern template hipError_t launch_fused_fast<false, false>(const KArgs&, const FusedBufs&, bool, bool, bool, bool, int,
+                                                           size_t, hipStream_t);
+extern template hipError_t launch_fused_fast<true, false>(const KArgs&, const FusedBufs&, bool, bool, bool, bool, int,
+                                                          size_t, hipStream_t);
+extern template hipError_t launch_fused_fast<false, true>(const KArgs&, const FusedBufs&, bool, bool, bool, bool, int,
+                                                          size_t, hipStream_t);
+extern template hipError_t launch_fused_fast<true, true>(const KArgs&, const FusedBufs&, bool, bool, bool, bool, int,
+                                                         size_t, hipStream_t);
 
 }  // namespace tfg_kern

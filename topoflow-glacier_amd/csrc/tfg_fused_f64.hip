@@ -18,7 +18,7 @@ namespace tfg_kern {
 hipError_t launch_fused_exact(const KArgs& a, const FusedBufs& b, bool read_depths, bool catchments, bool qc_on,
                               int blocks, size_t lds, hipStream_t stream) {
   constexpr int C = kCellsPerThread;
-#define TFG_ARGS a, b.uni, static_cast<const double*>(b.forc), static_cast<const double*>(b.stat), b.geo, b.catch_id, \
+#define TFG_ARGS a, b.uni, b.tab, static_cast<const double*>(b.forc), static_cast<const double*>(b.stat), b.geo, b.catch_id, \
                  b.st, b.tot, b.ring, static_cast<double*>(b.hist), b.slab, static_cast<const double*>(b.qc)
 #define TFG_LAUNCH(RD, CT, QC) \
   hipLaunchKernelGGL((k_fused<double, true, RD, CT, QC, C>), blocks, kBlock, lds, stream, TFG_ARGS)

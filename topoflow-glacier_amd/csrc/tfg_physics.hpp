@@ -1101,7 +1101,10 @@ __device__ __forceinline__ void melt_fast(const DevParams& p, QT Q_sum, float P_
 // in fp64 (tfg_set_flux(TFG_FLUX_F64)).  Eccs integrates E_in over a cold spell
 // and SM reads E_in - Eccs at melt onset, where the fp32 rounding of those
 // terms adds up; the fp32 form is the default.
-template <bool QC, bool NANSAFE, bool PREC = false>
+// SAT: the Satterlund vapour pressures (DevParams::satterlund, which the launch
+// dispatches on) instead of Brutsaert's, the default: a compile-time form, so
+// neither carries a load, branch or select for the option.
+template <bool QC, bool NANSAFE, bool PREC = false, bool SAT = false>
 __device__ inline void cell_step_fast(const DevParams& p, const CellStaticF& g, const tfg_uniforms* __restrict__ up,
                                       const tfg_uniforms& u, const double* __restrict__ geo_d, int64_t n_pad,
                                       int64_t cell, float P, float T_air, float Hum_sp, float P_air, float uz,
@@ -1122,9 +1125,9 @@ __device__ inline void cell_step_fast(const DevParams& p, const CellStaticF& g, 
   d.PS += P_snow;
   // vapour pressures [mbar] (:788-826); RH = e_air / e_sat_air (:838)
   // Brutsaert: e_sat = 6.11 exp(17.3 T/(T+237.3)); Satterlund: 10^(11.4-2353/T_K)/100
-  const float rA = p.satterlund ? rT : frcp(T_air + 237.3f);
+  const float rA = SAT ? rT : frcp(T_air + 237.3f);
   float inv_esat;
-  if (!p.satterlund) {
+  if (!SAT) {
     inv_esat = (1.0f / 6.11f) * fexp2((-17.3f * kLog2e) * T_air * rA);
   } else {
     inv_esat = 100.0f * fexp2((2353.0f * rT - 11.4f) * 3.3219280948873626f);
@@ -1196,8 +1199,8 @@ __device__ inline void cell_step_fast(const DevParams& p, const CellStaticF& g, 
     // (Brutsaert k = 17.3*237.3, c = 237.3; Satterlund k = 2353 ln 10, c = 273.15):
     // one unbiased exp2 of the exponent difference, so the remaining error is
     // random (v_exp_f32 rounding), not a bias that would accumulate in Eccs
-    const float rS = frcp(T_surf + (p.satterlund ? 273.15f : 237.3f));
-    const float xs2 = (p.satterlund ? -7816.4968f : -5922.6815f) * dTs * rS * rA;
+    const float rS = frcp(T_surf + (SAT ? 273.15f : 237.3f));
+    const float xs2 = (SAT ? -7816.4968f : -5922.6815f) * dTs * rS * rA;
     const float de = fmaf(-e_air, fexp2(xs2), e_air);
     Qh = p.f_rho_air_Cp_air * Dh * dTs;
     Qe = p.f_qe * Dh * de * fexp2(g.ek * rT);  // lhc / p0 folded
@@ -1265,7 +1268,7 @@ __device__ inline void cell_step_fast(const DevParams& p, const CellStaticF& g, 
   const float Qn_SW = K_cs * (1.0f - albedo);
   // longwave (:1167-1248): em_air - 1 (the balance below needs only that)
   float em_m1;
-  if (!p.satterlund) {
+  if (!SAT) {
     if constexpr (PREC) {
       em_m1 = 0.0f;  // fp64 below
     } else {
@@ -1285,7 +1288,7 @@ __device__ inline void cell_step_fast(const DevParams& p, const CellStaticF& g, 
     // em_air's seventh root by one Halley step from an fp32 seed (root7, the
     // fp64 engine's; Satterlund's em_air stays fp32), the balance in fp64
     const double TaK = Td + 273.15, TsK = Tsd + 273.15;
-    const double emd_m1 = p.satterlund ? (double)em_m1
+    const double emd_m1 = SAT ? (double)em_m1
                                        : fma(p.one_minus_F_172 * p.cloud_term, root7_p((e64 * 0.1) * rcp_nr1(TaK)), p.F - 1.0);
     const double ta2d = TaK * TaK;
     Qn_LW = p.em_surf_sigma * fma(emd_m1, ta2d * ta2d, dTd * (TaK + TsK) * fma(TsK, TsK, ta2d));
@@ -1299,7 +1302,14 @@ __device__ inline void cell_step_fast(const DevParams& p, const CellStaticF& g, 
   std::conditional_t<PREC, double, float> Q_sum;
   if constexpr (PREC) Q_sum = (((double)Qn_SW + Qn_LW) + Qh) + Qe + (QC ? (double)qc : 0.0);
   else {
-    Q_sum = Qn_SW + Qn_LW + Qh + Qe;
+    // Qn_SW + Qn_LW + Qh + Qe with the short-wave product fused into the first
+    // sum and written so: which of the two products the compiler contracts
+    // there is otherwise its choice, and it changes with the control flow
+    // around the step (it did when the Satterlund option became a template
+    // parameter), moving the last bit of Q_sum.  This is the form every
+    // instance has had; the products of Qh and Qe contract into the later sums
+    // either way.
+    Q_sum = fmaf(K_cs, 1.0f - albedo, Qn_LW) + Qh + Qe;
     if constexpr (QC) Q_sum = Q_sum + qc;
   }
 

@@ -181,9 +181,10 @@ def code_object_sha256(path: Path | None = None) -> str | None:
     return hashlib.sha256(blob).hexdigest() if blob else None
 
 
-BENCH_KERNEL = "_ZN8tfg_kern7k_fusedIfLb0ELb0ELb0ELb0ELi1ELb0ELb0E"  # k_fused<float, false, false, false, false, 1, false, false>
-BENCH_KERNEL_PREC = "_ZN8tfg_kern7k_fusedIfLb0ELb0ELb0ELb0ELi1ELb0ELb1E"  # ... the fp64-flux form (PREC = true)
-BENCH_KERNEL_F64 = "_ZN8tfg_kern7k_fusedIdLb1ELb0ELb0ELb0ELi1ELb0ELb0E"  # k_fused<double, true, false, false, false, 1, false, false>
+# the last argument is SAT = false: the Satterlund forms are other instances (tfg_fused_sat.hip, tfg_fused_prec_sat.hip)
+BENCH_KERNEL = "_ZN8tfg_kern7k_fusedIfLb0ELb0ELb0ELb0ELi1ELb0ELb0ELb0E"  # k_fused<float, false, false, false, false, 1, false, false, false>
+BENCH_KERNEL_PREC = "_ZN8tfg_kern7k_fusedIfLb0ELb0ELb0ELb0ELi1ELb0ELb1ELb0E"  # ... the fp64-flux form (PREC = true)
+BENCH_KERNEL_F64 = "_ZN8tfg_kern7k_fusedIdLb1ELb0ELb0ELb0ELi1ELb0ELb0ELb0E"  # k_fused<double, true, false, false, false, 1, false, false, false>
 
 
 def gfx950_code_objects(path: Path | None = None) -> list[bytes]:
