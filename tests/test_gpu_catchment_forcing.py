@@ -5,7 +5,8 @@ hydrograph.forced_catchment_hydrographs: the frames against the numpy
 restatement of the rule (tests/downscale_ref.py), the precipitation clamp,
 batches and the frame range, several tiles per workgroup, split launches,
 missing data, the humidity cap end to end, the hydrograph against the numpy
-oracle, and the rejected arguments.
+oracle, the rejected arguments, and the pinned staging ring it shares with
+tfg_set_inputs.
 
 Inputs.  tests/harness.py:bare_ice_inputs(4, 37, 100, 24): 3700 cells, 14 whole
 chunks and a ragged one.  Catchment map `divide`: id = 3 min(cell // 925, 3) +
@@ -484,3 +485,47 @@ def test_rejected_arguments_leave_the_frames_as_they_were():
         # and the handle still takes a good call: an all-off Downscale needs no z_ref
         e.set_catchment_forcing(t, downscale=_downscale())
         assert np.array_equal(read_frames(e, range(8)), t[:, :, inp.eff].astype(np.float32))
+
+
+# ------------------------------------------------------------------ 10. the staging ring of the two entry points
+@pytest.mark.parametrize("engine", ["float32", "float64"])
+def test_set_inputs_and_catchment_forcing_share_one_staging_ring(engine):
+    """tfg_set_inputs and tfg_set_catchment_forcing stage a host source through
+    one two-slot pinned ring.  Four calls with no sync in between, on 7 x 77 =
+    539 cells (plane stride 576, no multiple of 256): the largest request
+    (5 n doubles) into slot 0, the smallest (a table of 2 frames x 5 x 3
+    catchments) into slot 1, then 5 n floats into slot 0 again (kept: smaller)
+    and 5 n doubles into slot 1 (grown).  Each source is overwritten as soon as
+    its call returns: it was borrowed for the call only.  Every plane read back
+    equals what was sent, converted once to the engine's type, bit for bit."""
+    from topoflow_glacier import _native as nat
+
+    ny, nx, nc = 7, 77, 3
+    n = ny * nx
+    R = NP[engine]
+    rng = np.random.default_rng(539)
+    cid = (np.arange(n) % nc).astype(np.int32)
+    a0, a4 = rng.uniform(-3.0, 3.0, (2, 5, n))  # fp64 values that fp32 rounds
+    a3 = rng.uniform(-3.0, 3.0, (5, n)).astype(np.float32)
+    table = rng.uniform(-3.0, 3.0, (2, 5, nc))
+    want = np.stack([a0.astype(R), table[0][:, cid].astype(R), table[1][:, cid].astype(R), a3.astype(R), a4.astype(R)])
+    assert engine == "float64" or not np.array_equal(want[0].astype(np.float64), a0)  # the conversion is a real one
+    e = make_engine(BASE_CFG, ny, nx, engine, n_frames=5, hist_depth=1, n_catch=nc, fuse_steps=1)
+    try:
+        e.set_field("catch_id", cid)
+
+        def send_inputs(frame, src, code):
+            src = np.array(src)  # the call's own copy
+            e._chk(e.lib.tfg_set_inputs(e.h, frame, src.ctypes.data_as(ctypes.c_void_p), code, n, 0))
+            src.fill(np.nan)
+
+        send_inputs(0, a0, nat.F64)
+        t = np.array(table)
+        e._chk(e.lib.tfg_set_catchment_forcing(e.h, 1, 2, t.ctypes.data_as(ctypes.c_void_p), 0, None, None))
+        t.fill(np.nan)
+        send_inputs(3, a3, nat.F32)
+        send_inputs(4, a4, nat.F64)
+        got = read_frames(e, range(5))
+    finally:
+        e.close()
+    assert got.dtype == want.dtype and np.array_equal(got, want)

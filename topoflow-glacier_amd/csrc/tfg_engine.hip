@@ -18,6 +18,14 @@
 // -> k_diag_reduce when the diagnostics are read, which folds
 // the slab into the running fp64 totals in a fixed order (bitwise
 // reproducible).
+//
+// Layout: the one-cell kernels and the small grid kernels (with tfg_flow.hpp,
+// tfg_series.hpp, tfg_forcing.hpp); then the host layer.  What a handle owns
+// is a member that releases itself (Buf of tfg_hostbuf.hpp over three memory
+// policies, Event, Stream, StageRing, MappedBlock), so tfg_destroy is `delete`.
+// One definition each: by_type / by_types (the float | double instance of a
+// launch), read_flag and note_written (finite-data tracking), wait_flags,
+// step_args, kBmiToPlane.  Then the C ABI, in include/tfg.h's order.
 #include <hip/hip_runtime.h>
 #include <mutex>
 
@@ -37,6 +45,7 @@
 #include "tfg_physics.hpp"
 #include "tfg_conduction.hpp"
 #include "tfg_fused.hpp"
+#include "tfg_hostbuf.hpp"
 
 namespace {
 
@@ -102,6 +111,29 @@ __device__ __forceinline__ void store_one_cell(int64_t np, const CellState& cs, 
   srow[5] = tfg::npmax(sv[5], d.Pmax);
 }
 
+// The step's six history planes into history slot `slot`.
+__device__ __forceinline__ void store_one_hist(int64_t np, int slot, const CellOut& o, double* __restrict__ hist) {
+  double* h = hist + (int64_t)slot * kNumHist * np;
+  h[H_HSNOW * np] = o.h_snow;
+  h[H_SM * np] = o.SM;
+  h[H_HICE * np] = o.h_ice;
+  h[H_IM * np] = o.IM;
+  h[H_MTOT * np] = o.M_total;
+  h[H_RH * np] = o.RH;
+}
+
+// The step's eight BMI outputs: h_snow, h_swe, SM, h_ice, h_iwe, IM, M_total, RH.
+__device__ __forceinline__ void store_one_out(const CellState& cs, const CellOut& o, double* __restrict__ out) {
+  out[0] = o.h_snow;
+  out[1] = cs.h_swe;
+  out[2] = o.SM;
+  out[3] = o.h_ice;
+  out[4] = cs.h_iwe;
+  out[5] = o.IM;
+  out[6] = o.M_total;
+  out[7] = o.RH;
+}
+
 __global__ __launch_bounds__(64 * tfg::kCellWaves) void k_cell(const KArgs a, const CellIo io, const double* __restrict__ geo,
                                              const int32_t* __restrict__ catch_id, double* __restrict__ st,
                                              int64_t* __restrict__ tot, int32_t* __restrict__ ring,
@@ -141,26 +173,13 @@ __global__ __launch_bounds__(64 * tfg::kCellWaves) void k_cell(const KArgs a, co
 #endif
   if (threadIdx.x == 0) {
     ring[(int64_t)u.slot * np] = q_new;
-    double* h = hist + (int64_t)u.hist * kNumHist * np;
-    h[H_HSNOW * np] = o.h_snow;
-    h[H_SM * np] = o.SM;
-    h[H_HICE * np] = o.h_ice;
-    h[H_IM * np] = o.IM;
-    h[H_MTOT * np] = o.M_total;
-    h[H_RH * np] = o.RH;
+    store_one_hist(np, u.hist, o, hist);
     double* fr = forc + (int64_t)u.frame * kNumForc * np;
 #pragma unroll
     for (int f = 0; f < kNumForc; ++f) fr[f * np] = io.in[f];
     store_one_cell(np, cs, d, sv, st, tot, srow);
-    double* out = a.io_out;  // [8][1]: h_snow, h_swe, SM, h_ice, h_iwe, IM, M_total, RH
-    out[0] = o.h_snow;
-    out[1] = cs.h_swe;
-    out[2] = o.SM;
-    out[3] = o.h_ice;
-    out[4] = cs.h_iwe;
-    out[5] = o.IM;
-    out[6] = o.M_total;
-    out[7] = o.RH;
+    double* out = a.io_out;  // [8][1]
+    store_one_out(cs, o, out);
 #ifdef TFG_CELL_TIMING
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     const long long tt3 = wall_clock64();
@@ -227,13 +246,7 @@ __global__ __launch_bounds__(64 * tfg::kCellWaves) void k_cell_run(const KArgs a
     tfg::cell_step_exact_wave<tfg::kCellWaves>(p, sx, u, cur.v[F_P], cur.v[F_T], cur.v[F_Q], cur.v[F_PA], cur.v[F_UZ],
                                                 cur.q, q_new, cs, o, d, qc, lds_x);
     ring[(int64_t)u.slot * np] = q_new;
-    double* h = hist + (int64_t)u.hist * kNumHist * np;
-    h[H_HSNOW * np] = o.h_snow;
-    h[H_SM * np] = o.SM;
-    h[H_HICE * np] = o.h_ice;
-    h[H_IM * np] = o.IM;
-    h[H_MTOT * np] = o.M_total;
-    h[H_RH * np] = o.RH;
+    store_one_hist(np, u.hist, o, hist);
     cur = nxt;
   }
   store_one_cell(np, cs, d, sv, st, tot, srow);
@@ -298,26 +311,12 @@ __global__ __launch_bounds__(64 * tfg::kCellWaves) void k_cell_many(const CellJo
                                               job.in[F_UZ], q_old, q_new, cs, o, d, qc, lds_x);
   if (threadIdx.x == 0) {
     ring[(int64_t)job.u.slot * np] = q_new;
-    double* h = job.hist + (int64_t)job.u.hist * kNumHist * np;
-    h[H_HSNOW * np] = o.h_snow;
-    h[H_SM * np] = o.SM;
-    h[H_HICE * np] = o.h_ice;
-    h[H_IM * np] = o.IM;
-    h[H_MTOT * np] = o.M_total;
-    h[H_RH * np] = o.RH;
+    store_one_hist(np, job.u.hist, o, job.hist);
     double* fr = job.forc + (int64_t)job.u.frame * kNumForc * np;
 #pragma unroll
     for (int f = 0; f < kNumForc; ++f) fr[f * np] = job.in[f];
     store_one_cell(np, cs, d, sv, st, tot, srow);
-    double* ob = out + (int64_t)blockIdx.x * 8;  // h_snow, h_swe, SM, h_ice, h_iwe, IM, M_total, RH
-    ob[0] = o.h_snow;
-    ob[1] = cs.h_swe;
-    ob[2] = o.SM;
-    ob[3] = o.h_ice;
-    ob[4] = cs.h_iwe;
-    ob[5] = o.IM;
-    ob[6] = o.M_total;
-    ob[7] = o.RH;
+    store_one_out(cs, o, out + (int64_t)blockIdx.x * 8);
     __threadfence_system();
     __hip_atomic_store(flags + blockIdx.x, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
   }
@@ -574,6 +573,9 @@ __global__ void k_window_nan(const int64_t* __restrict__ tot, int64_t n, int32_t
 
 enum : uint8_t { kUnknown = 0, kOk = 1, kDirty = 2 };
 
+// BMI input order (P_air, Hum_sp, P, T_air, uz) -> plane of a device forcing frame, on the host
+constexpr int kBmiToPlane[5] = {F_PA, F_Q, F_P, F_T, F_UZ};
+
 // tfg_selftest_powers: the fp64 engine's power rewrites (tfg_physics.hpp) and
 // its exp / log / constant-divisor division (tfg_fastmath.hpp) on device, with
 // the device libm's exp and log beside them
@@ -601,75 +603,162 @@ __global__ void k_selftest_powers(const double* __restrict__ x, double* __restri
   }
 }
 
+// ===========================================================================
+// Host layer: what a handle owns
+// ===========================================================================
+namespace {
+
+using tfg_host::Buf;
+
+// The three kinds of memory the engine allocates (Buf's policies, tfg_hostbuf.hpp).
+// tfg_selftest_powers aside, these are the file's only allocation and free calls.
+struct DevMem {
+  static int alloc(void** p, size_t bytes) { return (int)hipMalloc(p, bytes); }
+  static int release(void* p) { return (int)hipFree(p); }
+};
+struct PinnedMem {
+  static int alloc(void** p, size_t bytes) { return (int)hipHostMalloc(p, bytes, hipHostMallocDefault); }
+  static int release(void* p) { return (int)hipHostFree(p); }
+};
+struct MappedMem {  // pinned, device-mapped and coherent: kernels read and write it in place
+  static int alloc(void** p, size_t bytes) { return (int)hipHostMalloc(p, bytes, hipHostMallocMapped | hipHostMallocCoherent); }
+  static int release(void* p) { return (int)hipHostFree(p); }
+};
+
+// A device buffer read as T: h->st + S_ALB * np, kernel arguments and `if (h->qc)` stay as with a raw pointer.
+template <class T>
+struct Dev : Buf<DevMem> {
+  operator T*() const { return static_cast<T*>(ptr); }
+  char* bytes() const { return static_cast<char*>(ptr); }  // for offsets in the engine's element size
+};
+
+// An event (timing off) and a non-blocking stream, created on first use and destroyed with their owner.
+template <class T, hipError_t (*Destroy)(T)>
+struct Owned {
+  T v = nullptr;
+  Owned() = default;
+  Owned(const Owned&) = delete;
+  Owned& operator=(const Owned&) = delete;
+  ~Owned() { if (v) (void)Destroy(v); }
+  operator T() const { return v; }
+};
+struct Event : Owned<hipEvent_t, hipEventDestroy> {
+  hipError_t create() { return v ? hipSuccess : hipEventCreateWithFlags(&v, hipEventDisableTiming); }
+};
+struct Stream : Owned<hipStream_t, hipStreamDestroy> {
+  hipError_t create() { return v ? hipSuccess : hipStreamCreateWithFlags(&v, hipStreamNonBlocking); }
+};
+
+// Two pinned slots for host data that is borrowed for one call only: the call
+// copies it into the slot whose previous transfer has completed and queues the
+// transfer from there (tfg_set_inputs and tfg_set_catchment_forcing share one
+// ring, each slot with a device buffer of its own; tfg_step stages its
+// uniforms through another, into d_u / d_u2).
+struct StageRing {
+  struct Slot {
+    Buf<PinnedMem> host;
+    Buf<DevMem> dev;
+    Event done;   // the slot's transfer on the handle's stream
+    Event done2;  // tfg_step only: its second copy, on the side stream
+  };
+  Slot slot[2];
+  int next = 0;
+  // The next slot, idle, with room for `bytes` (the old contents are not kept).
+  hipError_t acquire(size_t bytes, bool with_dev, Slot** out) {
+    Slot& s = slot[next];
+    next ^= 1;
+    hipError_t e = s.done.v ? hipEventSynchronize(s.done) : s.done.create();
+    if (e == hipSuccess && s.done2.v) e = hipEventSynchronize(s.done2);
+    if (e == hipSuccess) e = (hipError_t)s.host.reserve(bytes);
+    if (e == hipSuccess && with_dev) e = (hipError_t)s.dev.reserve(bytes);
+    *out = &s;
+    return e;
+  }
+  static hipError_t commit(Slot& s, hipStream_t stream) { return hipEventRecord(s.done, stream); }
+};
+
+// A pinned, device-mapped host block that kernels read their inputs from and
+// write their outputs and release flags to, zeroed when (re)allocated; the
+// launches that use it are numbered from 1, a fresh flag's 0 never among them.
+struct MappedBlock {
+  Buf<MappedMem> mem;
+  char* dev = nullptr;
+  uint32_t seq = 0;
+  char* host() const { return static_cast<char*>(mem.ptr); }
+  // Callers ask mem.cap < bytes first and wait for the launches that still use the block.
+  hipError_t reserve(size_t bytes) {
+    dev = nullptr;
+    seq = 0;
+    if (const int e = mem.reserve(bytes)) return (hipError_t)e;
+    std::memset(mem.ptr, 0, bytes);
+    const hipError_t e = hipHostGetDevicePointer((void**)&dev, mem.ptr, 0);
+    if (e != hipSuccess) (void)mem.reset();
+    return e;
+  }
+  uint32_t next_seq() { return ++seq ? seq : ++seq; }
+};
+
+}  // namespace
+
+// Every resource is an owning member: `delete h` releases them all, in reverse
+// order of declaration (the streams last), and an empty handle makes no HIP call.
 struct tfg_handle {
+  Stream own_stream, side;       // the handle's own stream, and a split launch's second part's (tfg_set_split)
+  hipStream_t stream = nullptr;  // own_stream, or the caller's (tfg_set_stream)
   int device = 0, engine = TFG_F32;
   int64_t ny = 0, nx = 0, n = 0, n_pad = 0;
   int n_frames = 1, hist_depth = 1, n_catch = 1, ring_len = 72;
   size_t rsz = 4;
   DevParams dp{};
-  hipStream_t own_stream = nullptr, stream = nullptr;
-  void* forc = nullptr;
-  void* stat = nullptr;
-  void* lwsw = nullptr;          // [2][n_pad] R, not read by the physics
-  float* geo = nullptr;          // fast engine: [5][n_pad] f32 + [2][n_pad] f64 solar geometry; exact: [kStaticPlanes][n_pad] f64 CellStatic
+  Dev<void> forc, stat;
+  Dev<void> lwsw;                // [2][n_pad] R, not read by the physics
+  Dev<float> geo;                // fast engine: [5][n_pad] f32 + [2][n_pad] f64 solar geometry; exact: [kStaticPlanes][n_pad] f64 CellStatic
                                  // (elev, cos_leq, sin_leq, dlon, tan_eq, cos_dlon, sin_dlon)
   bool geo_dirty = true;
-  int32_t* catch_id = nullptr;
-  double* st = nullptr;
-  int64_t* tot = nullptr;
-  int32_t* ring = nullptr;
-  void* hist = nullptr;
-  double* diag = nullptr;        // [n_catch][6]
-  double* slab = nullptr;        // [max_blocks][n_catch][6]
+  Dev<int32_t> catch_id;         // [n_pad], allocated (zeroed) by the first TFG_ST_CATCH_ID set
+  Dev<double> st;
+  Dev<int64_t> tot;
+  Dev<int32_t> ring;
+  Dev<void> hist;
+  Dev<double> diag;              // [n_catch][6]
+  Dev<double> slab;              // [max_blocks][n_catch][6]
   // tfg_catchment_series, allocated on first use: the workgroups' partial sums and a host call's result
-  double* series_part = nullptr; // [series_blocks][kSeriesBatch][n_catch]
-  double* series_out = nullptr;  // [hist_depth][n_catch]
-  float* d_diurnal = nullptr;
-  int32_t* d_flag = nullptr;
+  Dev<double> series_part;       // [series_blocks][kSeriesBatch][n_catch]
+  Dev<double> series_out;        // [hist_depth][n_catch]
+  Dev<float> d_diurnal;
+  Dev<int32_t> d_flag;
   // tfg_step's staged steps: [nsteps] tfg_uniforms, then the [nsteps] StepAddr
-  // records of the same steps (step_table, stage_bytes); d_u2 and h_u[] alike
-  tfg_uniforms* d_u = nullptr;
-  int64_t d_u_cap = 0;
-  tfg_uniforms* h_u[2] = {nullptr, nullptr};
-  hipEvent_t h_u_ev[2] = {nullptr, nullptr};
-  int64_t h_u_cap[2] = {0, 0};
-  int h_u_next = 0;
-  void* staging = nullptr;
-  size_t staging_bytes = 0;
+  // records of the same steps (step_table, stage_bytes); d_u2 and u_ring's slots alike
+  Dev<tfg_uniforms> d_u;
+  StageRing u_ring;
+  Dev<void> staging;             // upload / download's conversion scratch
   int max_blocks = 2048;
   int fuse = 24;
   bool depths_derived = false;
   bool slope_invalid = false;
   bool initialised = false;
   bool tot_dirty = false;        // window slots set through TFG_ST_WINDOW
-  double* wtmp = nullptr;        // [n_pad] f64 scratch for window I/O
-  double* halo = nullptr;        // [2][nx] f64 DEM halo rows (tfg_terrain_from_dem)
-  double* flow_halo = nullptr;   // [2 sides][2][nx] f64 ice-flow halo rows (s, H)
-  double* flow_edges = nullptr;  // [2 rows][2][nx] f64 this shard's edge rows
-  double* flow_red = nullptr;    // f64 per-workgroup maxima of k_ice_flow<R, true>
+  // scratch and halo rows, allocated on first use
+  Dev<double> wtmp;              // [n_pad] f64 scratch for window I/O
+  Dev<double> halo;              // [2][nx] f64 DEM halo rows (tfg_terrain_from_dem)
+  Dev<double> flow_halo;         // [2 sides][2][nx] f64 ice-flow halo rows (s, H)
+  Dev<double> flow_edges;        // [2 rows][2][nx] f64 this shard's edge rows
+  Dev<double> flow_red;          // f64 per-workgroup maxima of k_ice_flow<R, true>
   double flow_gamma = 0.0;       // 2A/(n+2) (rho_ice g)^n, n = 3 [m^-3 yr^-1]
   // optional lateral conduction: Qc plane (engine type) added to Q_sum while qc_on
-  void* qc = nullptr;            // [n_pad] R
+  Dev<void> qc;                  // [n_pad] R, allocated (zeroed) on first use
   bool qc_on = false;
-  double* cond_halo = nullptr;   // [2 sides][4][nx] f64 halo rows (T_snow, h_snow, T_ice, h_ice)
-  double* cond_edges = nullptr;  // [2 rows][4][nx] f64 this shard's edge rows
+  Dev<double> cond_halo;         // [2 sides][4][nx] f64 halo rows (T_snow, h_snow, T_ice, h_ice)
+  Dev<double> cond_edges;        // [2 rows][4][nx] f64 this shard's edge rows
   double inv_cs = 0.0, inv_ci = 0.0, h_active = 0.0;  // 1/(rho_s Cp_s), 1/(rho_i Cp_i h_al), h_al
-  // tfg_set_inputs: pinned host staging ring (2 slots) + device staging
-  void* in_h[2] = {nullptr, nullptr};
-  void* in_d[2] = {nullptr, nullptr};
-  size_t in_cap[2] = {0, 0};
-  hipEvent_t in_ev[2] = {nullptr, nullptr};
-  int in_next = 0;
+  // tfg_set_inputs and tfg_set_catchment_forcing: host sources go through this ring
+  StageRing in_ring;
   // tfg_get_outputs: device gather buffer + pinned host buffer
-  void* out_d = nullptr;
-  void* out_h = nullptr;
-  size_t out_cap = 0;
-  // tfg_update: one pinned host block (inputs | uniforms | outputs) that the
+  Dev<void> out_d;
+  Buf<PinnedMem> out_h;
+  // tfg_update: one block (inputs | uniforms | outputs | flags) that the
   // kernels read and write directly through its device mapping
-  char* io_h = nullptr;
-  char* io_d = nullptr;
-  size_t io_cap = 0;
-  uint32_t io_seq = 0;
+  MappedBlock io;
   int64_t last_hist = 0;
   // Finite-data tracking for the fp32 engine's two step forms (tfg_physics.hpp,
   // "Missing data"): a launch runs the clean form only when everything it reads
@@ -684,14 +773,11 @@ struct tfg_handle {
   int64_t ns_launches = 0;           // launches that ran the NaN-safe form (tfg_nan_safe_launches)
   bool force_ns = false;             // tfg_set_step_form(TFG_FORM_NAN_SAFE): every launch NaN-safe
   bool flux_f64 = false;             // tfg_set_flux(TFG_FLUX_F64): the fp32 engine's fp64-flux form
-  // Split launches (tfg_set_split): the second part's stream, its copy of the
-  // step uniforms, and the events that order it against the handle's stream
+  // Split launches (tfg_set_split): the side stream's copy of the step
+  // uniforms, and the events that order it against the handle's stream
   int split_mode = TFG_SPLIT_AUTO;
-  hipStream_t side = nullptr;
-  hipEvent_t side_fork = nullptr, side_join = nullptr;
-  tfg_uniforms* d_u2 = nullptr;
-  int64_t d_u2_cap = 0;
-  hipEvent_t h_u_ev2[2] = {nullptr, nullptr};
+  Event side_fork, side_join;
+  Dev<tfg_uniforms> d_u2;
   bool side_busy = false;   // the side stream holds launches the handle's stream is not yet ordered after
   bool side_stale = true;   // the handle's stream holds work the side stream's next launch must follow
   std::string err;
@@ -706,20 +792,33 @@ int fail(tfg_handle* h, int code, const std::string& msg) {
 
 #define HIPCHK(h, call)                                                                  \
   do {                                                                                   \
-    hipError_t e_ = (call);                                                              \
+    const hipError_t e_ = (hipError_t)(call); /* Buf passes HIP's codes on as int */    \
     if (e_ != hipSuccess)                                                                \
       return fail((h), TFG_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
   } while (0)
 
 size_t dtype_size(int dt) { return dt == TFG_F64 ? 8 : 4; }
 
-// The Qc plane, allocated (zeroed) on first use.
-int ensure_qc(tfg_handle* h) {
-  if (h->qc) return TFG_OK;
-  HIPCHK(h, hipMalloc(&h->qc, (size_t)h->n_pad * h->rsz));
-  HIPCHK(h, hipMemsetAsync(h->qc, 0, (size_t)h->n_pad * h->rsz, h->stream));
+// Run f(Tag<float>) or f(Tag<double>) by a TFG_F32 / TFG_F64 dtype (the
+// handle's engine type, mostly): one spelling of a launch for both instances
+// of a kernel.  by_types: the same over a pair of dtypes.
+template <class T> struct Tag { using type = T; };
+template <class F>
+decltype(auto) by_type(int dtype, F&& f) { return dtype == TFG_F32 ? f(Tag<float>{}) : f(Tag<double>{}); }
+template <class F>
+decltype(auto) by_types(int dt_a, int dt_b, F&& f) {
+  return by_type(dt_a, [&](auto a) { return by_type(dt_b, [&](auto b) { return f(a, b); }); });
+}
+
+// A buffer allocated on first use and zero-filled then (a later call finds it large enough).
+template <class B>
+int reserve_zeroed(tfg_handle* h, B& b, size_t bytes) {
+  if (bytes <= b.cap) return TFG_OK;
+  HIPCHK(h, b.reserve(bytes));
+  HIPCHK(h, hipMemsetAsync(b.ptr, 0, bytes, h->stream));
   return TFG_OK;
 }
+int ensure_qc(tfg_handle* h) { return reserve_zeroed(h, h->qc, (size_t)h->n_pad * h->rsz); }
 
 // Split launches (include/tfg.h tfg_set_split).  The parts are whole 256-cell
 // chunks; AUTO splits grids of one to 64 rounds of the resident workgroups.
@@ -755,20 +854,11 @@ int api_sync(tfg_handle* h) {
   return join_side(h);
 }
 int ensure_side(tfg_handle* h) {
-  if (h->side) return TFG_OK;
-  HIPCHK(h, hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking));
-  HIPCHK(h, hipEventCreateWithFlags(&h->side_fork, hipEventDisableTiming));
-  HIPCHK(h, hipEventCreateWithFlags(&h->side_join, hipEventDisableTiming));
+  if (h->side.v) return TFG_OK;
+  HIPCHK(h, h->side.create());
+  HIPCHK(h, h->side_fork.create());
+  HIPCHK(h, h->side_join.create());
   h->side_stale = true;
-  return TFG_OK;
-}
-
-int ensure_staging(tfg_handle* h, size_t bytes) {
-  if (bytes <= h->staging_bytes) return TFG_OK;
-  if (h->staging) HIPCHK(h, hipFree(h->staging));
-  h->staging = nullptr;
-  HIPCHK(h, hipMalloc(&h->staging, bytes));
-  h->staging_bytes = bytes;
   return TFG_OK;
 }
 
@@ -783,60 +873,83 @@ bool forcing_wide() {
 
 int grid_for(int64_t n) { return (int)std::min<int64_t>(std::max<int64_t>((n + 255) / 256, 1), 8192); }
 
+// dst (type dt) <- src (type st), both on the device, the two types different
+int convert(tfg_handle* h, void* dst, int dt, const void* src, int st, int64_t n) {
+  if (!((dt == TFG_F32 && st == TFG_F64) || (dt == TFG_F64 && st == TFG_F32)))
+    return fail(h, TFG_ERR_ARG, "unsupported dtype conversion");
+  by_types(dt, st, [&](auto d, auto s) {
+    using D = typename decltype(d)::type;
+    using S = typename decltype(s)::type;
+    if constexpr (!std::is_same_v<D, S>)
+      hipLaunchKernelGGL((k_convert<D, S>), grid_for(n), 256, 0, h->stream, (D*)dst, (const S*)src, n);
+  });
+  HIPCHK(h, hipGetLastError());
+  return TFG_OK;
+}
+
 // copy n elements of type st (host/device) into device buffer dst of type dt
 int upload(tfg_handle* h, void* dst, int dt, const void* src, int st, int64_t n, int on_dev) {
   if (n <= 0) return TFG_OK;
   const size_t sbytes = (size_t)n * dtype_size(st);
   if (dt == st) {
     HIPCHK(h, hipMemcpyAsync(dst, src, sbytes, on_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
-    if (!on_dev) HIPCHK(h, hipStreamSynchronize(h->stream));
-    return TFG_OK;
+  } else {
+    if (!on_dev) {
+      HIPCHK(h, h->staging.reserve(sbytes));
+      HIPCHK(h, hipMemcpyAsync(h->staging, src, sbytes, hipMemcpyHostToDevice, h->stream));
+      src = h->staging;
+    }
+    if (int rc = convert(h, dst, dt, src, st, n)) return rc;
   }
-  const void* dsrc = src;
-  if (!on_dev) {
-    int rc = ensure_staging(h, sbytes);
-    if (rc) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->staging, src, sbytes, hipMemcpyHostToDevice, h->stream));
-    dsrc = h->staging;
-  }
-  const int gb = grid_for(n);
-  if (dt == TFG_F32 && st == TFG_F64)
-    hipLaunchKernelGGL((k_convert<float, double>), gb, 256, 0, h->stream, (float*)dst, (const double*)dsrc, n);
-  else if (dt == TFG_F64 && st == TFG_F32)
-    hipLaunchKernelGGL((k_convert<double, float>), gb, 256, 0, h->stream, (double*)dst, (const float*)dsrc, n);
-  else
-    return fail(h, TFG_ERR_ARG, "unsupported dtype conversion");
-  HIPCHK(h, hipGetLastError());
   if (!on_dev) HIPCHK(h, hipStreamSynchronize(h->stream));
   return TFG_OK;
 }
 
-// kOk when every value of `planes` planes of n cells (stride `stride`
-// elements) at device pointer p is finite, kDirty otherwise (synchronous).
-int check_finite(tfg_handle* h, const void* p, int dtype, int64_t n, uint8_t* out, int planes = 1, int64_t stride = 0) {
+// Whether the kernel(s) `launch` queues on the handle's stream set d_flag[0] (synchronous).
+template <class Launch>
+int read_flag(tfg_handle* h, bool* set, Launch&& launch) {
   HIPCHK(h, hipMemsetAsync(h->d_flag, 0, 4, h->stream));
-  if (dtype == TFG_F64)
-    hipLaunchKernelGGL((k_nonfinite<double>), grid_for(n), 256, 0, h->stream, (const double*)p, n, stride, planes, h->d_flag);
-  else
-    hipLaunchKernelGGL((k_nonfinite<float>), grid_for(n), 256, 0, h->stream, (const float*)p, n, stride, planes, h->d_flag);
+  launch();
   HIPCHK(h, hipGetLastError());
   int32_t flag = 0;
   HIPCHK(h, hipMemcpyAsync(&flag, h->d_flag, 4, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  *out = flag ? kDirty : kOk;
+  *set = flag != 0;
   return TFG_OK;
 }
 
-// The same check on host values (the BMI inputs of tfg_update / tfg_set_inputs).
-template <class T>
-uint8_t host_finite(const T* p, int64_t n) {
+// kOk when every value of n cells at device pointer p is finite, kDirty otherwise (synchronous).
+int check_finite(tfg_handle* h, const void* p, int dtype, int64_t n, uint8_t* out) {
   bool bad = false;
-  for (int64_t i = 0; i < n; ++i) bad |= !std::isfinite(p[i]);
-  return bad ? kDirty : kOk;
+  int rc = read_flag(h, &bad, [&] {
+    by_type(dtype, [&](auto t) {
+      using T = typename decltype(t)::type;
+      hipLaunchKernelGGL((k_nonfinite<T>), grid_for(n), 256, 0, h->stream, (const T*)p, n, (int64_t)0, 1, h->d_flag);
+    });
+  });
+  if (rc == TFG_OK) *out = bad ? kDirty : kOk;
+  return rc;
 }
-// fp64 host values the fp32 engine will hold: finite after the conversion (a
-// finite double beyond FLT_MAX becomes inf in the frame)
-uint8_t host_finite_as_f32(const double* p, int64_t n) {
+
+// Finite-data status of the n cells just written at device pointer p
+// (tfg_handle::plane_state; the fp32 engine only).  A device source keeps the
+// set stream-ordered: kUnknown, checked before a launch long enough to pay for
+// it (choose_form).  A host source is checked now (its upload was synchronous).
+// sticky: `state` covers more than this plane (state_state), so only a bad one shows.
+int note_written(tfg_handle* h, const void* p, int dtype, int64_t n, bool on_dev, uint8_t* state, bool sticky = false) {
+  if (h->engine != TFG_F32) return TFG_OK;
+  uint8_t st = kUnknown;
+  if (!on_dev)
+    if (int rc = check_finite(h, p, dtype, n, &st)) return rc;
+  if (!sticky || st != kOk) *state = st;
+  return TFG_OK;
+}
+
+// The same check on host values as the fp32 engine will hold them (the BMI
+// inputs of tfg_update / tfg_set_inputs, a table's rows): finite after the
+// conversion (a finite double beyond FLT_MAX becomes inf in the frame).
+template <class T>
+uint8_t host_finite_as_f32(const T* p, int64_t n) {
   bool bad = false;
   for (int64_t i = 0; i < n; ++i) bad |= !std::isfinite((float)p[i]);
   return bad ? kDirty : kOk;
@@ -849,18 +962,10 @@ int download(tfg_handle* h, void* dst, int dt, const void* src, int st, int64_t 
   if (dt != st) {
     void* conv = dst;
     if (!on_dev) {
-      int rc = ensure_staging(h, dbytes);
-      if (rc) return rc;
+      HIPCHK(h, h->staging.reserve(dbytes));
       conv = h->staging;
     }
-    const int gb = grid_for(n);
-    if (dt == TFG_F32 && st == TFG_F64)
-      hipLaunchKernelGGL((k_convert<float, double>), gb, 256, 0, h->stream, (float*)conv, (const double*)src, n);
-    else if (dt == TFG_F64 && st == TFG_F32)
-      hipLaunchKernelGGL((k_convert<double, float>), gb, 256, 0, h->stream, (double*)conv, (const float*)src, n);
-    else
-      return fail(h, TFG_ERR_ARG, "unsupported dtype conversion");
-    HIPCHK(h, hipGetLastError());
+    if (int rc = convert(h, conv, dt, src, st, n)) return rc;
     if (on_dev) return TFG_OK;
     dsrc = conv;
   }
@@ -966,11 +1071,11 @@ void derive_params(const tfg_params& q, DevParams& p) {
 void* field_ptr(tfg_handle* h, int field, int index, int* dtype) {
   const int64_t np = h->n_pad;
   const size_t rs = h->rsz;
-  char* f = static_cast<char*>(h->forc);
-  char* hs = static_cast<char*>(h->hist);
+  char* f = h->forc.bytes();
+  char* hs = h->hist.bytes();
   switch (field) {
-    case TFG_IN_LW_IN: *dtype = h->engine; return static_cast<char*>(h->lwsw);
-    case TFG_IN_SW_IN: *dtype = h->engine; return static_cast<char*>(h->lwsw) + np * rs;
+    case TFG_IN_LW_IN: *dtype = h->engine; return h->lwsw.bytes();
+    case TFG_IN_SW_IN: *dtype = h->engine; return h->lwsw.bytes() + np * rs;
     case TFG_IN_P: *dtype = h->engine; return f + ((int64_t)index * kNumForc + F_P) * np * rs;
     case TFG_IN_T_AIR: *dtype = h->engine; return f + ((int64_t)index * kNumForc + F_T) * np * rs;
     case TFG_IN_HUM_SP: *dtype = h->engine; return f + ((int64_t)index * kNumForc + F_Q) * np * rs;
@@ -984,9 +1089,9 @@ void* field_ptr(tfg_handle* h, int field, int index, int* dtype) {
     case TFG_OUT_RH: *dtype = h->engine; return hs + ((int64_t)index * kNumHist + H_RH) * np * rs;
     case TFG_OUT_H_SWE: *dtype = TFG_F64; return h->st + S_HSWE * np;
     case TFG_OUT_H_IWE: *dtype = TFG_F64; return h->st + S_HIWE * np;
-    case TFG_ST_ELEV: *dtype = h->engine; return static_cast<char*>(h->stat);
-    case TFG_ST_SLOPE: *dtype = h->engine; return static_cast<char*>(h->stat) + np * rs;
-    case TFG_ST_ASPECT: *dtype = h->engine; return static_cast<char*>(h->stat) + 2 * np * rs;
+    case TFG_ST_ELEV: *dtype = h->engine; return h->stat.bytes();
+    case TFG_ST_SLOPE: *dtype = h->engine; return h->stat.bytes() + np * rs;
+    case TFG_ST_ASPECT: *dtype = h->engine; return h->stat.bytes() + 2 * np * rs;
     case TFG_ST_CATCH_ID: *dtype = TFG_I32; return h->catch_id;
     case TFG_ST_ECCS: *dtype = TFG_F64; return h->st + S_ECCS * np;
     case TFG_ST_ECCI: *dtype = TFG_F64; return h->st + S_ECCI * np;
@@ -1016,10 +1121,8 @@ struct Part {
   hipStream_t stream;
 };
 
-template <class R, bool EXACT>
-int launch_fused(tfg_handle* h, const tfg_uniforms* d_u, const StepAddr* d_t, int K, int blocks, size_t lds,
-                 const IoArgs& io, bool ns, const Part* part = nullptr) {
-  const hipStream_t stream = part ? part->stream : h->stream;
+// The KArgs of K steps over the handle's whole plane stride (a part of a split launch narrows them).
+KArgs step_args(const tfg_handle* h, int K, const IoArgs& io) {
   KArgs a;
   a.p = h->dp;
   a.K = K;
@@ -1028,18 +1131,30 @@ int launch_fused(tfg_handle* h, const tfg_uniforms* d_u, const StepAddr* d_t, in
   a.io_flag = io.flag;
   a.io_seq = io.seq;
   a.n_catch = h->n_catch;
-  a.n = part ? part->n_valid : h->n;
+  a.n = h->n;
   a.n_pad = h->n_pad;
-  a.n_step = part ? part->cells : h->n_pad;
+  a.n_step = h->n_pad;
+  return a;
+}
+
+template <class R, bool EXACT>
+int launch_fused(tfg_handle* h, const tfg_uniforms* d_u, const StepAddr* d_t, int K, int blocks, size_t lds,
+                 const IoArgs& io, bool ns, const Part* part = nullptr) {
+  const hipStream_t stream = part ? part->stream : h->stream;
+  KArgs a = step_args(h, K, io);
+  if (part) {
+    a.n = part->n_valid;
+    a.n_step = part->cells;
+  }
   // a part's buffers start at its first cell in every plane (the planes keep
   // their stride); the kernel corrects its two mixed-width views by c0
   const int64_t c0 = part ? part->c0 : 0;
   a.part_c0 = c0;
   const size_t rb = (size_t)c0 * h->rsz;
-  const FusedBufs fb = {d_u, d_t, static_cast<const char*>(h->forc) + rb, static_cast<const char*>(h->stat) + rb, h->geo + c0,
+  const FusedBufs fb = {d_u, d_t, h->forc.bytes() + rb, h->stat.bytes() + rb, h->geo + c0,
                         h->catch_id ? h->catch_id + c0 : nullptr, h->st + c0, h->tot + c0, h->ring + c0,
-                        static_cast<char*>(h->hist) + rb, h->slab + (part ? part->slab_row0 : 0) * h->n_catch * 6,
-                        h->qc ? static_cast<const char*>(h->qc) + rb : nullptr};
+                        h->hist.bytes() + rb, h->slab + (part ? part->slab_row0 : 0) * h->n_catch * 6,
+                        h->qc ? h->qc.bytes() + rb : nullptr};
   const bool rd = !h->depths_derived;
   const bool ct = h->catch_id != nullptr;
   if constexpr (EXACT) {  // the fp64 engine's instantiations live in tfg_fused_f64.hip
@@ -1175,30 +1290,30 @@ int tfg_create(const tfg_params* p, int64_t ny, int64_t nx, int engine, int devi
   // no more workgroups (slab rows) than the grid has chunks: a one-cell BMI
   // handle keeps one row, not 32768 (NextGen may hold thousands of handles)
   h->max_blocks = (int)std::min<int64_t>(h->max_blocks, (h->n_pad / kCellsPerThread + kBlock - 1) / kBlock);
-  if (hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking) != hipSuccess) { h->err = "stream create failed"; return bail(TFG_ERR_HIP); }
+  if (h->own_stream.create() != hipSuccess) { h->err = "stream create failed"; return bail(TFG_ERR_HIP); }
   h->stream = h->own_stream;
   const int64_t np = h->n_pad;
   const size_t rs = h->rsz;
-  struct A { void** p; size_t bytes; } allocs[] = {
+  struct A { Buf<DevMem>* b; size_t bytes; } allocs[] = {
       {&h->forc, (size_t)n_frames * kNumForc * np * rs},
       {&h->stat, 3 * (size_t)np * rs},
       {&h->lwsw, 2 * (size_t)np * rs},
-      {(void**)&h->geo, engine == TFG_F32 ? (size_t)np * (tfg::kGeoF * 4 + 2 * 8) : (size_t)np * tfg::kStaticPlanes * 8},
-      {(void**)&h->st, (size_t)kNumState * np * 8},
-      {(void**)&h->tot, (size_t)np * 8},
-      {(void**)&h->ring, (size_t)p->ring_len * np * 4},
+      {&h->geo, engine == TFG_F32 ? (size_t)np * (tfg::kGeoF * 4 + 2 * 8) : (size_t)np * tfg::kStaticPlanes * 8},
+      {&h->st, (size_t)kNumState * np * 8},
+      {&h->tot, (size_t)np * 8},
+      {&h->ring, (size_t)p->ring_len * np * 4},
       {&h->hist, (size_t)hist_depth * kNumHist * np * rs},
-      {(void**)&h->diag, (size_t)n_catch * 6 * 8},
-      {(void**)&h->slab, (size_t)h->max_blocks * n_catch * 6 * 8},
-      {(void**)&h->d_flag, (size_t)n_frames * kNumForc * 4},  // a flag per forcing plane (choose_form)
+      {&h->diag, (size_t)n_catch * 6 * 8},
+      {&h->slab, (size_t)h->max_blocks * n_catch * 6 * 8},
+      {&h->d_flag, (size_t)n_frames * kNumForc * 4},  // a flag per forcing plane (choose_form)
   };
   for (auto& a : allocs) {
-    hipError_t e = hipMalloc(a.p, a.bytes);
+    const hipError_t e = (hipError_t)a.b->reserve(a.bytes);
     if (e != hipSuccess) {
       h->err = std::string("hipMalloc(") + std::to_string(a.bytes) + " B) failed: " + hipGetErrorString(e);
       return bail(TFG_ERR_HIP);
     }
-    if (hipMemsetAsync(*a.p, 0, a.bytes, h->stream) != hipSuccess) { h->err = "hipMemset failed"; return bail(TFG_ERR_HIP); }
+    if (hipMemsetAsync(a.b->ptr, 0, a.bytes, h->stream) != hipSuccess) { h->err = "hipMemset failed"; return bail(TFG_ERR_HIP); }
   }
   if (hipStreamSynchronize(h->stream) != hipSuccess) { h->err = "sync failed"; return bail(TFG_ERR_HIP); }
   h->plane_state.assign((size_t)n_frames * kNumForc, kOk);  // zero-filled: finite
@@ -1213,33 +1328,14 @@ int tfg_destroy(tfg_handle* h) {
   if (h->stream && h->stream != h->own_stream) (void)hipStreamSynchronize(h->stream);
   if (h->own_stream) (void)hipStreamSynchronize(h->own_stream);
   if (h->side) (void)hipStreamSynchronize(h->side);
-  void* ptrs[] = {h->forc, h->stat, h->lwsw, h->geo, h->catch_id, h->st, h->tot, h->ring, h->hist, h->diag, h->wtmp, h->halo,
-                  h->flow_halo, h->flow_edges, h->flow_red, h->qc, h->cond_halo, h->cond_edges,
-                  h->slab, h->series_part, h->series_out, h->d_diurnal, h->d_flag, h->d_u, h->d_u2, h->staging};
-  for (void* q : ptrs) if (q) (void)hipFree(q);
-  for (int i = 0; i < 2; ++i) {
-    if (h->h_u[i]) (void)hipHostFree(h->h_u[i]);
-    if (h->h_u_ev[i]) (void)hipEventDestroy(h->h_u_ev[i]);
-    if (h->h_u_ev2[i]) (void)hipEventDestroy(h->h_u_ev2[i]);
-    if (h->in_h[i]) (void)hipHostFree(h->in_h[i]);
-    if (h->in_d[i]) (void)hipFree(h->in_d[i]);
-    if (h->in_ev[i]) (void)hipEventDestroy(h->in_ev[i]);
-  }
-  if (h->out_d) (void)hipFree(h->out_d);
-  if (h->out_h) (void)hipHostFree(h->out_h);
-  if (h->io_h) (void)hipHostFree(h->io_h);
-  if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
-  if (h->side_fork) (void)hipEventDestroy(h->side_fork);
-  if (h->side_join) (void)hipEventDestroy(h->side_join);
-  if (h->side) (void)hipStreamDestroy(h->side);
-  delete h;
+  delete h;  // the members release what they own
   return TFG_OK;
 }
 
 int tfg_set_stream(tfg_handle* h, void* stream) {
   if (int rc_ = api_sync(h)) return rc_;  // after a split launch's second part
   if (!h) return fail(nullptr, TFG_ERR_ARG, "null handle");
-  h->stream = stream ? static_cast<hipStream_t>(stream) : h->own_stream;
+  h->stream = stream ? static_cast<hipStream_t>(stream) : h->own_stream.v;
   return TFG_OK;
 }
 
@@ -1338,42 +1434,29 @@ int tfg_set_field(tfg_handle* h, int field, int index, const void* src, int src_
     }
     for (int64_t i = 0; i < n; ++i)
       if (hs[i] < 0 || hs[i] >= h->n_catch) return fail(h, TFG_ERR_ARG, "catchment id out of [0, n_catch)");
-    if (!h->catch_id) {
-      HIPCHK(h, hipMalloc((void**)&h->catch_id, (size_t)h->n_pad * 4));
-      HIPCHK(h, hipMemsetAsync(h->catch_id, 0, (size_t)h->n_pad * 4, h->stream));
-    }
+    if (int rc = reserve_zeroed(h, h->catch_id, (size_t)h->n_pad * 4)) return rc;
     HIPCHK(h, hipMemcpyAsync(h->catch_id, src, (size_t)n * 4, src_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return TFG_OK;
   }
   if (src_dtype != TFG_F32 && src_dtype != TFG_F64) return fail(h, TFG_ERR_ARG, "src dtype must be TFG_F32/TFG_F64");
-  const bool track = h->engine == TFG_F32;  // finite-data tracking (tfg_handle::plane_state)
   if (field == TFG_ST_QC) {  // a caller-supplied conduction flux: on until tfg_conduction_off
     if (int rc = ensure_qc(h)) return rc;
     if (int rc = upload(h, h->qc, h->engine, src, src_dtype, n, src_on_device)) return rc;
     h->qc_on = true;
-    // device sources stay stream-ordered: their status is checked lazily before a launch (choose_form)
-    if (track && src_on_device) h->qc_state = kUnknown;
-    else if (track) return check_finite(h, h->qc, h->engine, n, &h->qc_state);
-    return TFG_OK;
+    return note_written(h, h->qc, h->engine, n, src_on_device, &h->qc_state);
   }
   if (field == TFG_ST_WINDOW) {
     if (index < 0 || index >= h->ring_len) return fail(h, TFG_ERR_ARG, "window slot out of range");
-    if (!h->wtmp) HIPCHK(h, hipMalloc((void**)&h->wtmp, (size_t)h->n_pad * 8));
+    HIPCHK(h, h->wtmp.reserve((size_t)h->n_pad * 8));
     int rc = upload(h, h->wtmp, TFG_F64, src, src_dtype, n, src_on_device);
     if (rc) return rc;
     hipLaunchKernelGGL(k_window_set, grid_for(n), 256, 0, h->stream, h->ring + (int64_t)index * h->n_pad, h->wtmp, n,
                        h->dp.qscale);
     HIPCHK(h, hipGetLastError());
     h->tot_dirty = true;
-    if (track && src_on_device) {
-      h->state_state = kUnknown;  // checked lazily (choose_form -> check_state reads the rebuilt totals)
-    } else if (track) {  // a NaN slot makes the window dirty; a finite one leaves the state's status as it was
-      uint8_t st = kOk;
-      if (int rc = check_finite(h, h->wtmp, TFG_F64, n, &st)) return rc;
-      if (st != kOk) h->state_state = kDirty;
-    }
-    return TFG_OK;
+    // a NaN slot makes the window dirty; a device source is checked lazily (check_state reads the rebuilt totals)
+    return note_written(h, h->wtmp, TFG_F64, n, src_on_device, &h->state_state, true);
   }
   int fdt = 0;
   void* dst = field_ptr(h, field, index, &fdt);
@@ -1390,52 +1473,36 @@ int tfg_set_field(tfg_handle* h, int field, int index, const void* src, int src_
     double* sd = h->st + (field == TFG_OUT_H_SNOW ? S_HSNOW : S_HICE) * h->n_pad;
     int rc = upload(h, sd, TFG_F64, src, src_dtype, n, src_on_device);
     if (rc) return rc;
-    if (track && src_on_device) {
-      h->state_state = kUnknown;
-    } else if (track) {
-      uint8_t st = kOk;
-      if (int rc2 = check_finite(h, sd, TFG_F64, n, &st)) return rc2;
-      if (st != kOk) h->state_state = kDirty;
-    }
+    if (int rc2 = note_written(h, sd, TFG_F64, n, src_on_device, &h->state_state, true)) return rc2;
     return upload(h, dst, fdt, src, src_dtype, n, src_on_device);
   }
   int rc = upload(h, dst, fdt, src, src_dtype, n, src_on_device);
   if (rc) return rc;
-  // Finite-data status of what was written (tfg_handle::plane_state).  A host
-  // source is checked now (its upload is synchronous anyway); a device source
-  // keeps the set stream-ordered and non-blocking: its plane is marked
-  // unknown and checked lazily before a launch long enough to pay for it
-  // (choose_form), or the launch runs the NaN-safe form.
+  // finite-data status of what was written (note_written)
   const bool state_field = field == TFG_OUT_H_SWE || field == TFG_OUT_H_IWE || field == TFG_ST_ECCS ||
                            field == TFG_ST_ECCI || field == TFG_ST_ALBEDO || field == TFG_ST_NDAYS;
-  if (track && is_frame_field(field)) {
+  uint8_t* status = nullptr;
+  if (is_frame_field(field)) {
     const int plane = field == TFG_IN_P ? F_P : field == TFG_IN_T_AIR ? F_T : field == TFG_IN_HUM_SP ? F_Q
                     : field == TFG_IN_P_AIR ? F_PA : F_UZ;
-    uint8_t* ps = &h->plane_state[(size_t)index * kNumForc + plane];
-    if (src_on_device) *ps = kUnknown;
-    else if (int rc2 = check_finite(h, dst, fdt, n, ps)) return rc2;
-  } else if (track && field == TFG_ST_ELEV) {
-    if (src_on_device) h->elev_state = kUnknown;
-    else if (int rc2 = check_finite(h, dst, fdt, n, &h->elev_state)) return rc2;
-  } else if (track && state_field && src_on_device) {
-    h->state_state = kUnknown;
-  } else if (track && state_field) {
-    uint8_t st = kOk;
-    if (int rc2 = check_finite(h, dst, fdt, n, &st)) return rc2;
-    if (st != kOk) h->state_state = kDirty;
+    status = &h->plane_state[(size_t)index * kNumForc + plane];
+  } else if (field == TFG_ST_ELEV) {
+    status = &h->elev_state;
+  } else if (state_field) {
+    status = &h->state_state;
   }
+  if (status)
+    if (int rc2 = note_written(h, dst, fdt, n, src_on_device, status, state_field)) return rc2;
   if (field == TFG_ST_ELEV || field == TFG_ST_SLOPE || field == TFG_ST_ASPECT) h->geo_dirty = true;
   if (field == TFG_ST_SLOPE) {
-    HIPCHK(h, hipMemsetAsync(h->d_flag, 0, 4, h->stream));
-    if (h->engine == TFG_F32)
-      hipLaunchKernelGGL((k_check_slope<float>), grid_for(n), 256, 0, h->stream, (const float*)dst, n, h->d_flag);
-    else
-      hipLaunchKernelGGL((k_check_slope<double>), grid_for(n), 256, 0, h->stream, (const double*)dst, n, h->d_flag);
-    int32_t flag = 0;
-    HIPCHK(h, hipMemcpyAsync(&flag, h->d_flag, 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->slope_invalid = flag != 0;
-    if (flag) return fail(h, TFG_ERR_DOMAIN, "ERROR: some slope angles are out of range (beta not in [0, pi/2]; bmi_topoflow_glacier.py:1106-1111)");
+    if (int rc2 = read_flag(h, &h->slope_invalid, [&] {
+          by_type(h->engine, [&](auto t) {
+            using R = typename decltype(t)::type;
+            hipLaunchKernelGGL((k_check_slope<R>), grid_for(n), 256, 0, h->stream, (const R*)dst, n, h->d_flag);
+          });
+        }))
+      return rc2;
+    if (h->slope_invalid) return fail(h, TFG_ERR_DOMAIN, "ERROR: some slope angles are out of range (beta not in [0, pi/2]; bmi_topoflow_glacier.py:1106-1111)");
   }
   return TFG_OK;
 }
@@ -1472,7 +1539,7 @@ int tfg_get_field(tfg_handle* h, int field, int index, void* dst, int dst_dtype,
   }
   if (field == TFG_ST_WINDOW) {
     if (index < 0 || index >= h->ring_len) return fail(h, TFG_ERR_ARG, "window slot out of range");
-    if (!h->wtmp) HIPCHK(h, hipMalloc((void**)&h->wtmp, (size_t)h->n_pad * 8));
+    HIPCHK(h, h->wtmp.reserve((size_t)h->n_pad * 8));
     hipLaunchKernelGGL(k_window_get, grid_for(n), 256, 0, h->stream, h->wtmp, h->ring + (int64_t)index * h->n_pad, n,
                        1.0 / h->dp.qscale);
     HIPCHK(h, hipGetLastError());
@@ -1542,12 +1609,14 @@ int prepare_steps(tfg_handle* h) {
     h->tot_dirty = false;
   }
   if (h->geo_dirty) {
-    if (h->engine == TFG_F32)
-      hipLaunchKernelGGL((k_prepare_geo<float>), grid_for(h->n_pad), 256, 0, h->stream, h->dp, (const float*)h->stat,
-                         h->geo, h->n_pad);
-    else
-      hipLaunchKernelGGL((k_prepare_static<double>), grid_for(h->n_pad), 256, 0, h->stream, h->dp,
-                         (const double*)h->stat, reinterpret_cast<double*>(h->geo), h->n_pad);
+    by_type(h->engine, [&](auto t) {  // the fast engine's solar geometry, the exact engine's CellStatic planes
+      using R = typename decltype(t)::type;
+      if constexpr (std::is_same_v<R, float>)
+        hipLaunchKernelGGL((k_prepare_geo<R>), grid_for(h->n_pad), 256, 0, h->stream, h->dp, (const R*)h->stat.ptr, h->geo, h->n_pad);
+      else
+        hipLaunchKernelGGL((k_prepare_static<R>), grid_for(h->n_pad), 256, 0, h->stream, h->dp, (const R*)h->stat.ptr,
+                           (double*)h->geo.ptr, h->n_pad);
+    });
     HIPCHK(h, hipGetLastError());
     h->geo_dirty = false;
   }
@@ -1561,36 +1630,23 @@ constexpr int kVerifySteps = 8;
 // The state's finite-data status: the fp64 state planes and the window totals
 // (after prepare_steps has rebuilt them).  Synchronous.
 int check_state(tfg_handle* h) {
-  uint8_t st = kOk;
-  {  // the state planes, the albedo plane in the engine's type (fp32 for the fp32 engine)
-    const int64_t np = h->n_pad;
-    HIPCHK(h, hipMemsetAsync(h->d_flag, 0, 4, h->stream));
-    hipLaunchKernelGGL((k_nonfinite<double>), grid_for(h->n), 256, 0, h->stream, (const double*)h->st, h->n, np, S_ALB, h->d_flag);
-    if (h->engine == TFG_F32)
-      hipLaunchKernelGGL((k_nonfinite<float>), grid_for(h->n), 256, 0, h->stream, (const float*)(h->st + S_ALB * np), h->n,
-                         (int64_t)0, 1, h->d_flag);
-    else
-      hipLaunchKernelGGL((k_nonfinite<double>), grid_for(h->n), 256, 0, h->stream, (const double*)(h->st + S_ALB * np), h->n,
-                         (int64_t)0, 1, h->d_flag);
-    hipLaunchKernelGGL((k_nonfinite<double>), grid_for(h->n), 256, 0, h->stream, (const double*)(h->st + (S_ALB + 1) * np),
-                       h->n, np, kNumState - S_ALB - 1, h->d_flag);
-    HIPCHK(h, hipGetLastError());
-    int32_t flag = 0;
-    HIPCHK(h, hipMemcpyAsync(&flag, h->d_flag, 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    st = flag ? kDirty : kOk;
-  }
-  if (st == kOk) {
-    HIPCHK(h, hipMemsetAsync(h->d_flag, 0, 4, h->stream));
-    hipLaunchKernelGGL(k_window_nan, grid_for(h->n), 256, 0, h->stream, h->tot, h->n, h->d_flag);
-    HIPCHK(h, hipGetLastError());
-    int32_t flag = 0;
-    HIPCHK(h, hipMemcpyAsync(&flag, h->d_flag, 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    st = flag ? kDirty : kOk;
-  }
-  h->state_state = st;
-  return TFG_OK;
+  const int64_t np = h->n_pad;
+  const int gb = grid_for(h->n);
+  bool bad = false;
+  // the state planes, the albedo plane in the engine's type (fp32 for the fp32 engine)
+  int rc = read_flag(h, &bad, [&] {
+    hipLaunchKernelGGL((k_nonfinite<double>), gb, 256, 0, h->stream, (const double*)h->st, h->n, np, S_ALB, h->d_flag);
+    by_type(h->engine, [&](auto t) {
+      using R = typename decltype(t)::type;
+      hipLaunchKernelGGL((k_nonfinite<R>), gb, 256, 0, h->stream, (const R*)(h->st + S_ALB * np), h->n, (int64_t)0, 1, h->d_flag);
+    });
+    hipLaunchKernelGGL((k_nonfinite<double>), gb, 256, 0, h->stream, (const double*)(h->st + (S_ALB + 1) * np), h->n, np,
+                       kNumState - S_ALB - 1, h->d_flag);
+  });
+  if (rc == TFG_OK && !bad)
+    rc = read_flag(h, &bad, [&] { hipLaunchKernelGGL(k_window_nan, gb, 256, 0, h->stream, h->tot, h->n, h->d_flag); });
+  if (rc == TFG_OK) h->state_state = bad ? kDirty : kOk;
+  return rc;
 }
 
 // The fp32 engine's step form for one launch of K steps (tfg_physics.hpp,
@@ -1621,7 +1677,7 @@ int choose_form(tfg_handle* h, const tfg_uniforms* u, int K, const IoArgs& io, b
         HIPCHK(h, hipMemsetAsync(h->d_flag, 0, (size_t)nf * kNumForc * 4, h->stream));
         const dim3 grid(std::max(1, std::min(grid_for(h->n), 2048)), kNumForc);
         for (int j = 0; j < nf; ++j) {
-          const char* fp = static_cast<const char*>(h->forc) + (size_t)h->chk_frames[j] * kNumForc * h->n_pad * h->rsz;
+          const char* fp = h->forc.bytes() + (size_t)h->chk_frames[j] * kNumForc * h->n_pad * h->rsz;
           hipLaunchKernelGGL((k_nonfinite_planes<float>), grid, 256, 0, h->stream, (const float*)fp, h->n, h->n_pad,
                              h->d_flag + j * kNumForc);
         }
@@ -1653,6 +1709,13 @@ int choose_form(tfg_handle* h, const tfg_uniforms* u, int K, const IoArgs& io, b
   *ns = h->force_ns ||
         !(inputs_ok && h->state_state == kOk && h->elev_state == kOk && (!h->qc_on || h->qc_state == kOk));
   return TFG_OK;
+}
+
+// After a launch of the fp32 engine: the NaN-safe form may have carried missing data into the state.
+void note_form(tfg_handle* h, bool ns) {
+  if (!ns) return;
+  ++h->ns_launches;
+  if (h->state_state == kOk) h->state_state = kUnknown;
 }
 
 // The step table of u[0 .. nsteps) (tfg_fused.hpp, StepAddr): byte offsets in
@@ -1689,20 +1752,9 @@ int launch_steps(tfg_handle* h, const tfg_uniforms* d_u, const StepAddr* d_t, co
     const int K = (int)std::min<int64_t>(fuse, nsteps - k0);
     int rc = TFG_OK;
     if (one_cell) {
-      KArgs a;
-      a.p = h->dp;
-      a.K = K;
-      a.n_catch = h->n_catch;
-      a.n = h->n;
-      a.n_pad = h->n_pad;
-      a.n_step = h->n_pad;
-      a.io_in = nullptr;
-      a.io_out = nullptr;
-      a.io_flag = nullptr;
-      a.io_seq = 0;
-      hipLaunchKernelGGL(k_cell_run, 1, 64 * tfg::kCellWaves, 0, h->stream, a, d_u + k0, reinterpret_cast<const double*>(h->geo),
-                         h->catch_id, h->st, h->tot, h->ring, static_cast<const double*>(h->forc),
-                         static_cast<double*>(h->hist), h->slab, h->qc_on ? static_cast<const double*>(h->qc) : nullptr,
+      hipLaunchKernelGGL(k_cell_run, 1, 64 * tfg::kCellWaves, 0, h->stream, step_args(h, K, io), d_u + k0,
+                         (const double*)h->geo.ptr, h->catch_id, h->st, h->tot, h->ring, (const double*)h->forc.ptr,
+                         (double*)h->hist.ptr, h->slab, h->qc_on ? (const double*)h->qc.ptr : nullptr,
                          h->depths_derived ? 0 : 1);
       HIPCHK(h, hipGetLastError());
     } else if (h->engine == TFG_F32 && split && !io.in) {
@@ -1723,19 +1775,12 @@ int launch_steps(tfg_handle* h, const tfg_uniforms* d_u, const StepAddr* d_t, co
       if ((rc = launch_fused<float, false>(h, d_u + k0, d_t + k0, K, bA, lds, io, ns, &pa))) return rc;
       if ((rc = launch_fused<float, false>(h, h->d_u2 + k0, d_t2 + k0, K, bB, lds, io, ns, &pb))) return rc;
       h->side_busy = true;
-      if (ns) {
-        ++h->ns_launches;
-        if (h->state_state == kOk) h->state_state = kUnknown;
-      }
+      note_form(h, ns);
     } else if (h->engine == TFG_F32) {
       bool ns = true;
       if ((rc = choose_form(h, u + k0, K, io, &ns))) return rc;
       rc = launch_fused<float, false>(h, d_u + k0, d_t + k0, K, blocks, lds, io, ns);
-      if (ns) {
-        ++h->ns_launches;
-        // the NaN-safe form may have carried missing data into the state
-        if (h->state_state == kOk) h->state_state = kUnknown;
-      }
+      note_form(h, ns);
     } else {
       rc = launch_fused<double, true>(h, d_u + k0, d_t + k0, K, blocks, lds, io, false);
     }
@@ -1760,41 +1805,28 @@ int tfg_step(tfg_handle* h, const tfg_uniforms* u, int64_t nsteps) {
     return rc;
   }
   // stage uniforms: pinned double buffer -> device array (and the side stream's copy)
-  const int b = h->h_u_next;
-  h->h_u_next ^= 1;
-  if (h->h_u_ev[b]) HIPCHK(h, hipEventSynchronize(h->h_u_ev[b]));
-  else HIPCHK(h, hipEventCreateWithFlags(&h->h_u_ev[b], hipEventDisableTiming));
-  if (h->h_u_ev2[b]) HIPCHK(h, hipEventSynchronize(h->h_u_ev2[b]));
-  if (h->h_u_cap[b] < nsteps) {
-    if (h->h_u[b]) HIPCHK(h, hipHostFree(h->h_u[b]));
-    h->h_u[b] = nullptr;
-    HIPCHK(h, hipHostMalloc((void**)&h->h_u[b], stage_bytes(nsteps), hipHostMallocDefault));
-    h->h_u_cap[b] = nsteps;
-  }
-  if (h->d_u_cap < nsteps) {
+  const size_t bytes = stage_bytes(nsteps);
+  StageRing::Slot* s = nullptr;
+  HIPCHK(h, h->u_ring.acquire(bytes, false, &s));
+  if (h->d_u.cap < bytes) {
     // the previous launches may still read d_u: wait before reallocating
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->d_u) HIPCHK(h, hipFree(h->d_u));
-    h->d_u = nullptr;
-    HIPCHK(h, hipMalloc((void**)&h->d_u, stage_bytes(nsteps)));
-    h->d_u_cap = nsteps;
+    HIPCHK(h, h->d_u.reserve(bytes));
   }
   // the uniforms and, right after them, their step table: one copy
-  std::memcpy(h->h_u[b], u, (size_t)nsteps * sizeof(tfg_uniforms));
-  step_table(h, u, nsteps, reinterpret_cast<StepAddr*>(h->h_u[b] + nsteps));
-  HIPCHK(h, hipMemcpyAsync(h->d_u, h->h_u[b], stage_bytes(nsteps), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipEventRecord(h->h_u_ev[b], h->stream));
+  tfg_uniforms* h_u = static_cast<tfg_uniforms*>(s->host.ptr);
+  std::memcpy(h_u, u, (size_t)nsteps * sizeof(tfg_uniforms));
+  step_table(h, u, nsteps, reinterpret_cast<StepAddr*>(h_u + nsteps));
+  HIPCHK(h, hipMemcpyAsync(h->d_u, h_u, bytes, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, StageRing::commit(*s, h->stream));
   if (split) {
-    if (h->d_u2_cap < nsteps) {
+    if (h->d_u2.cap < bytes) {
       HIPCHK(h, hipStreamSynchronize(h->side));  // its launches may still read d_u2
-      if (h->d_u2) HIPCHK(h, hipFree(h->d_u2));
-      h->d_u2 = nullptr;
-      HIPCHK(h, hipMalloc((void**)&h->d_u2, stage_bytes(nsteps)));
-      h->d_u2_cap = nsteps;
+      HIPCHK(h, h->d_u2.reserve(bytes));
     }
-    if (!h->h_u_ev2[b]) HIPCHK(h, hipEventCreateWithFlags(&h->h_u_ev2[b], hipEventDisableTiming));
-    HIPCHK(h, hipMemcpyAsync(h->d_u2, h->h_u[b], stage_bytes(nsteps), hipMemcpyHostToDevice, h->side));
-    HIPCHK(h, hipEventRecord(h->h_u_ev2[b], h->side));
+    HIPCHK(h, s->done2.create());
+    HIPCHK(h, hipMemcpyAsync(h->d_u2, h_u, bytes, hipMemcpyHostToDevice, h->side));
+    HIPCHK(h, hipEventRecord(s->done2, h->side));
   }
   return launch_steps(h, h->d_u, table_of(h->d_u, nsteps), split ? table_of(h->d_u2, nsteps) : nullptr, u, nsteps, IoArgs(),
                       split);
@@ -1827,9 +1859,8 @@ int tfg_catchment_series(tfg_handle* h, int field, int hist0, int nslots, double
   HIPCHK(h, hipSetDevice(h->device));
   const int blocks = series_blocks(h->n, h->n_catch);
   const int row_len = kSeriesBatch * h->n_catch;
-  if (!h->series_part) HIPCHK(h, hipMalloc((void**)&h->series_part, (size_t)blocks * row_len * 8));
-  if (!out_on_device && !h->series_out)
-    HIPCHK(h, hipMalloc((void**)&h->series_out, (size_t)h->hist_depth * h->n_catch * 8));
+  HIPCHK(h, h->series_part.reserve((size_t)blocks * row_len * 8));
+  if (!out_on_device) HIPCHK(h, h->series_out.reserve((size_t)h->hist_depth * h->n_catch * 8));
   double* dout = out_on_device ? out : h->series_out;
   int fdt = 0;
   const void* plane = field_ptr(h, field, 0, &fdt);  // slot 0's plane of the field, engine type
@@ -1838,17 +1869,15 @@ int tfg_catchment_series(tfg_handle* h, int field, int hist0, int nslots, double
   for (int j0 = 0; j0 < nslots; j0 += kSeriesBatch) {
     const int nb = std::min(kSeriesBatch, nslots - j0);
     const int slot0 = (hist0 + j0) % h->hist_depth;
-    auto launch = [&](auto kern, auto* pl) {
-      hipLaunchKernelGGL(kern, blocks, kBlock, lds, h->stream, pl, stride, h->hist_depth, slot0, nb, h->catch_id, h->n,
-                         h->n_catch, h->series_part);
-    };
-    if (h->engine == TFG_F32) {
-      if (h->catch_id) launch(k_catch_series<float, true>, (const float*)plane);
-      else launch(k_catch_series<float, false>, (const float*)plane);
-    } else {
-      if (h->catch_id) launch(k_catch_series<double, true>, (const double*)plane);
-      else launch(k_catch_series<double, false>, (const double*)plane);
-    }
+    by_type(h->engine, [&](auto t) {
+      using R = typename decltype(t)::type;
+      auto launch = [&](auto kern) {
+        hipLaunchKernelGGL(kern, blocks, kBlock, lds, h->stream, (const R*)plane, stride, h->hist_depth, slot0, nb,
+                           h->catch_id, h->n, h->n_catch, h->series_part);
+      };
+      if (h->catch_id) launch(k_catch_series<R, true>);
+      else launch(k_catch_series<R, false>);
+    });
     HIPCHK(h, hipGetLastError());
     const int nent = nb * h->n_catch;
     hipLaunchKernelGGL(k_series_reduce, (nent + 15) / 16, kBlock, 0, h->stream, h->series_part, blocks, row_len, nent,
@@ -1919,15 +1948,13 @@ int tfg_fill_synthetic(tfg_handle* h, uint64_t seed, int64_t row0, int64_t nx_gl
   if (n_frames != h->n_frames) return fail(h, TFG_ERR_ARG, "n_frames mismatch");
   if (nx_global != h->nx) return fail(h, TFG_ERR_ARG, "row-block shards must span full rows (nx_global == nx)");
   HIPCHK(h, hipSetDevice(h->device));
-  if (!h->d_diurnal) HIPCHK(h, hipMalloc((void**)&h->d_diurnal, (size_t)n_frames * 4));
+  HIPCHK(h, h->d_diurnal.reserve((size_t)n_frames * 4));
   HIPCHK(h, hipMemcpyAsync(h->d_diurnal, diurnal, (size_t)n_frames * 4, hipMemcpyHostToDevice, h->stream));
-  const int gb = grid_for(h->n);
-  if (h->engine == TFG_F32)
-    hipLaunchKernelGGL((k_fill_synthetic<float>), gb, 256, 0, h->stream, (float*)h->forc, (float*)h->stat, h->st,
+  by_type(h->engine, [&](auto t) {
+    using R = typename decltype(t)::type;
+    hipLaunchKernelGGL((k_fill_synthetic<R>), grid_for(h->n), 256, 0, h->stream, (R*)h->forc.ptr, (R*)h->stat.ptr, h->st,
                        h->n, h->n_pad, h->nx, row0, nx_global, seed, h->d_diurnal, n_frames);
-  else
-    hipLaunchKernelGGL((k_fill_synthetic<double>), gb, 256, 0, h->stream, (double*)h->forc, (double*)h->stat, h->st,
-                       h->n, h->n_pad, h->nx, row0, nx_global, seed, h->d_diurnal, n_frames);
+  });
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->slope_invalid = false;
@@ -1954,39 +1981,24 @@ int tfg_set_inputs(tfg_handle* h, int frame, const void* src, int src_dtype, int
   HIPCHK(h, hipSetDevice(h->device));
   const size_t bytes = (size_t)5 * n * dtype_size(src_dtype);
   const void* dsrc = src;
-  int b = -1;
-  if (!src_on_device) {
-    // the host buffer is borrowed for this call only: copy it into a pinned
-    // slot whose previous transfer has completed, then transfer asynchronously
-    b = h->in_next;
-    h->in_next ^= 1;
-    if (h->in_ev[b]) HIPCHK(h, hipEventSynchronize(h->in_ev[b]));
-    else HIPCHK(h, hipEventCreateWithFlags(&h->in_ev[b], hipEventDisableTiming));
-    if (h->in_cap[b] < bytes) {
-      if (h->in_h[b]) HIPCHK(h, hipHostFree(h->in_h[b]));
-      if (h->in_d[b]) HIPCHK(h, hipFree(h->in_d[b]));
-      h->in_h[b] = h->in_d[b] = nullptr;
-      h->in_cap[b] = 0;
-      HIPCHK(h, hipHostMalloc(&h->in_h[b], bytes, hipHostMallocDefault));
-      HIPCHK(h, hipMalloc(&h->in_d[b], bytes));
-      h->in_cap[b] = bytes;
-    }
-    std::memcpy(h->in_h[b], src, bytes);
-    HIPCHK(h, hipMemcpyAsync(h->in_d[b], h->in_h[b], bytes, hipMemcpyHostToDevice, h->stream));
-    dsrc = h->in_d[b];
+  StageRing::Slot* s = nullptr;
+  if (!src_on_device) {  // borrowed for this call only: through the staging ring
+    HIPCHK(h, h->in_ring.acquire(bytes, true, &s));
+    std::memcpy(s->host.ptr, src, bytes);
+    HIPCHK(h, hipMemcpyAsync(s->dev.ptr, s->host.ptr, bytes, hipMemcpyHostToDevice, h->stream));
+    dsrc = s->dev.ptr;
   }
   if (h->engine == TFG_F32) {  // finite-data tracking: host inputs are checked here, device inputs later
-    static const int map[5] = {F_PA, F_Q, F_P, F_T, F_UZ};  // BMI order -> frame planes
     for (int f = 0; f < 5; ++f) {
       uint8_t st = kUnknown;
       if (!src_on_device)
         st = src_dtype == TFG_F64 ? host_finite_as_f32(static_cast<const double*>(src) + (size_t)f * n, n)
-                                  : host_finite(static_cast<const float*>(src) + (size_t)f * n, n);
-      h->plane_state[(size_t)frame * kNumForc + map[f]] = st;
+                                  : host_finite_as_f32(static_cast<const float*>(src) + (size_t)f * n, n);
+      h->plane_state[(size_t)frame * kNumForc + kBmiToPlane[f]] = st;
     }
   }
   if (int rc = launch_scatter(h, frame, dsrc, src_dtype, n)) return rc;
-  if (b >= 0) HIPCHK(h, hipEventRecord(h->in_ev[b], h->stream));
+  if (s) HIPCHK(h, StageRing::commit(*s, h->stream));
   return TFG_OK;
 }
 
@@ -2011,38 +2023,25 @@ int tfg_set_catchment_forcing(tfg_handle* h, int frame0, int nframes, const doub
   const size_t frame_len = (size_t)5 * h->n_catch;  // table entries per frame
   const double* dtab = table;
   const double* dz = on ? z_ref : nullptr;
-  int b = -1;
+  StageRing::Slot* s = nullptr;
   if (!table_on_device) {
-    // borrowed for this call only, like tfg_set_inputs' src: table | z_ref into a
-    // pinned slot whose previous transfer has completed, then one queued copy
+    // borrowed for this call only, like tfg_set_inputs' src: table | z_ref
+    // through the staging ring, one queued copy
     const size_t tbytes = (size_t)nframes * frame_len * 8, bytes = tbytes + (on ? (size_t)h->n_catch * 8 : 0);
-    b = h->in_next;
-    h->in_next ^= 1;
-    if (h->in_ev[b]) HIPCHK(h, hipEventSynchronize(h->in_ev[b]));
-    else HIPCHK(h, hipEventCreateWithFlags(&h->in_ev[b], hipEventDisableTiming));
-    if (h->in_cap[b] < bytes) {
-      if (h->in_h[b]) HIPCHK(h, hipHostFree(h->in_h[b]));
-      if (h->in_d[b]) HIPCHK(h, hipFree(h->in_d[b]));
-      h->in_h[b] = h->in_d[b] = nullptr;
-      h->in_cap[b] = 0;
-      HIPCHK(h, hipHostMalloc(&h->in_h[b], bytes, hipHostMallocDefault));
-      HIPCHK(h, hipMalloc(&h->in_d[b], bytes));
-      h->in_cap[b] = bytes;
-    }
-    std::memcpy(h->in_h[b], table, tbytes);
-    if (on) std::memcpy(static_cast<char*>(h->in_h[b]) + tbytes, z_ref, (size_t)h->n_catch * 8);
-    HIPCHK(h, hipMemcpyAsync(h->in_d[b], h->in_h[b], bytes, hipMemcpyHostToDevice, h->stream));
-    dtab = static_cast<const double*>(h->in_d[b]);
+    HIPCHK(h, h->in_ring.acquire(bytes, true, &s));
+    std::memcpy(s->host.ptr, table, tbytes);
+    if (on) std::memcpy(static_cast<char*>(s->host.ptr) + tbytes, z_ref, (size_t)h->n_catch * 8);
+    HIPCHK(h, hipMemcpyAsync(s->dev.ptr, s->host.ptr, bytes, hipMemcpyHostToDevice, h->stream));
+    dtab = static_cast<const double*>(s->dev.ptr);
     if (on) dz = dtab + (size_t)nframes * frame_len;
   }
   if (h->engine == TFG_F32) {
     // finite-data tracking: a plain gather of a host table leaves in a plane
     // exactly its table row's values (every cell is written), so the row
     // decides; a device table or a downscaled plane is checked lazily
-    static const int map[5] = {F_PA, F_Q, F_P, F_T, F_UZ};  // table order -> frame planes
     for (int j = 0; j < nframes; ++j)
-      for (int f = 0; f < 5; ++f)
-        h->plane_state[(size_t)(frame0 + j) * kNumForc + map[f]] =
+      for (int f = 0; f < 5; ++f)  // the table's rows are in BMI order
+        h->plane_state[(size_t)(frame0 + j) * kNumForc + kBmiToPlane[f]] =
             (table_on_device || on) ? kUnknown : host_finite_as_f32(table + (size_t)j * frame_len + (size_t)f * h->n_catch, h->n_catch);
   }
   ForcingDs d{};
@@ -2059,25 +2058,21 @@ int tfg_set_catchment_forcing(tfg_handle* h, int frame0, int nframes, const doub
   const bool wide = forcing_wide();
   for (int j0 = 0; j0 < nframes; j0 += kForcingBatch) {
     const int nb = std::min(kForcingBatch, nframes - j0);
-    char* fr = static_cast<char*>(h->forc) + (size_t)(frame0 + j0) * kNumForc * h->n_pad * h->rsz;
+    char* fr = h->forc.bytes() + (size_t)(frame0 + j0) * kNumForc * h->n_pad * h->rsz;
     const double* tb = dtab + (size_t)j0 * frame_len;
-    auto launch = [&](auto kern, auto* frp, int v) {
-      using RP = std::remove_pointer_t<decltype(frp)>;
-      hipLaunchKernelGGL(kern, forcing_blocks(h->n, v), kBlock, 0, h->stream, frp, h->n_pad, nb, tb, dz,
-                         static_cast<const RP*>(h->stat), h->catch_id, h->n, h->n_catch, d);
-    };
-    if (h->engine == TFG_F32) {
-      float* p = reinterpret_cast<float*>(fr);
-      if (wide) { if (on) launch(k_forcing_expand<float, true, 4>, p, 4); else launch(k_forcing_expand<float, false, 4>, p, 4); }
-      else { if (on) launch(k_forcing_expand<float, true, 1>, p, 1); else launch(k_forcing_expand<float, false, 1>, p, 1); }
-    } else {
-      double* p = reinterpret_cast<double*>(fr);
-      if (wide) { if (on) launch(k_forcing_expand<double, true, 2>, p, 2); else launch(k_forcing_expand<double, false, 2>, p, 2); }
-      else { if (on) launch(k_forcing_expand<double, true, 1>, p, 1); else launch(k_forcing_expand<double, false, 1>, p, 1); }
-    }
+    by_type(h->engine, [&](auto t) {
+      using R = typename decltype(t)::type;
+      constexpr int V = 16 / (int)sizeof(R);  // cells per lane of the wide form
+      auto launch = [&](auto kern, int v) {
+        hipLaunchKernelGGL(kern, forcing_blocks(h->n, v), kBlock, 0, h->stream, (R*)fr, h->n_pad, nb, tb, dz,
+                           (const R*)h->stat.ptr, h->catch_id, h->n, h->n_catch, d);
+      };
+      if (wide) { if (on) launch(k_forcing_expand<R, true, V>, V); else launch(k_forcing_expand<R, false, V>, V); }
+      else { if (on) launch(k_forcing_expand<R, true, 1>, 1); else launch(k_forcing_expand<R, false, 1>, 1); }
+    });
     HIPCHK(h, hipGetLastError());
   }
-  if (b >= 0) HIPCHK(h, hipEventRecord(h->in_ev[b], h->stream));
+  if (s) HIPCHK(h, StageRing::commit(*s, h->stream));
   return TFG_OK;
 }
 
@@ -2085,33 +2080,26 @@ namespace {
 
 // frame <- src[5][n] (device-visible pointer)
 int launch_scatter(tfg_handle* h, int frame, const void* dsrc, int src_dtype, int64_t n) {
-  char* fr = static_cast<char*>(h->forc) + (size_t)frame * kNumForc * h->n_pad * h->rsz;
-  const int gb = grid_for(n);
-  if (h->engine == TFG_F32 && src_dtype == TFG_F32)
-    hipLaunchKernelGGL((k_scatter_inputs<float, float>), gb, 256, 0, h->stream, (float*)fr, (const float*)dsrc, n, h->n_pad);
-  else if (h->engine == TFG_F32)
-    hipLaunchKernelGGL((k_scatter_inputs<float, double>), gb, 256, 0, h->stream, (float*)fr, (const double*)dsrc, n, h->n_pad);
-  else if (src_dtype == TFG_F32)
-    hipLaunchKernelGGL((k_scatter_inputs<double, float>), gb, 256, 0, h->stream, (double*)fr, (const float*)dsrc, n, h->n_pad);
-  else
-    hipLaunchKernelGGL((k_scatter_inputs<double, double>), gb, 256, 0, h->stream, (double*)fr, (const double*)dsrc, n, h->n_pad);
+  char* fr = h->forc.bytes() + (size_t)frame * kNumForc * h->n_pad * h->rsz;
+  by_types(h->engine, src_dtype, [&](auto r, auto s) {
+    using R = typename decltype(r)::type;
+    using S = typename decltype(s)::type;
+    hipLaunchKernelGGL((k_scatter_inputs<R, S>), grid_for(n), 256, 0, h->stream, (R*)fr, (const S*)dsrc, n, h->n_pad);
+  });
   HIPCHK(h, hipGetLastError());
   return TFG_OK;
 }
 
 // dst[8][n] (device-visible pointer) <- outputs of history slot `hist`
 int launch_gather(tfg_handle* h, int hist, void* gdst, int dst_dtype, int64_t n) {
-  const char* hs = static_cast<const char*>(h->hist) + (size_t)hist * kNumHist * h->n_pad * h->rsz;
+  const char* hs = h->hist.bytes() + (size_t)hist * kNumHist * h->n_pad * h->rsz;
   const int from_state = h->depths_derived ? 0 : 1;
-  const int gb = grid_for(n);
-  if (h->engine == TFG_F32 && dst_dtype == TFG_F32)
-    hipLaunchKernelGGL((k_gather_outputs<float, float>), gb, 256, 0, h->stream, (float*)gdst, (const float*)hs, h->st, n, h->n_pad, from_state);
-  else if (h->engine == TFG_F32)
-    hipLaunchKernelGGL((k_gather_outputs<float, double>), gb, 256, 0, h->stream, (double*)gdst, (const float*)hs, h->st, n, h->n_pad, from_state);
-  else if (dst_dtype == TFG_F32)
-    hipLaunchKernelGGL((k_gather_outputs<double, float>), gb, 256, 0, h->stream, (float*)gdst, (const double*)hs, h->st, n, h->n_pad, from_state);
-  else
-    hipLaunchKernelGGL((k_gather_outputs<double, double>), gb, 256, 0, h->stream, (double*)gdst, (const double*)hs, h->st, n, h->n_pad, from_state);
+  by_types(h->engine, dst_dtype, [&](auto r, auto d) {
+    using R = typename decltype(r)::type;
+    using D = typename decltype(d)::type;
+    hipLaunchKernelGGL((k_gather_outputs<R, D>), grid_for(n), 256, 0, h->stream, (D*)gdst, (const R*)hs, h->st, n, h->n_pad,
+                       from_state);
+  });
   HIPCHK(h, hipGetLastError());
   return TFG_OK;
 }
@@ -2129,22 +2117,15 @@ int tfg_get_outputs(tfg_handle* h, int hist, void* dst, int dst_dtype, int64_t n
   const size_t bytes = (size_t)8 * n * dtype_size(dst_dtype);
   void* gdst = dst;
   if (!dst_on_device) {
-    if (h->out_cap < bytes) {
-      if (h->out_d) HIPCHK(h, hipFree(h->out_d));
-      if (h->out_h) HIPCHK(h, hipHostFree(h->out_h));
-      h->out_d = h->out_h = nullptr;
-      h->out_cap = 0;
-      HIPCHK(h, hipMalloc(&h->out_d, bytes));
-      HIPCHK(h, hipHostMalloc(&h->out_h, bytes, hipHostMallocDefault));
-      h->out_cap = bytes;
-    }
+    HIPCHK(h, h->out_d.reserve(bytes));  // the call is synchronous: nothing queued still uses them
+    HIPCHK(h, h->out_h.reserve(bytes));
     gdst = h->out_d;
   }
   if (int rc = launch_gather(h, hist, gdst, dst_dtype, n)) return rc;
   if (!dst_on_device) {
-    HIPCHK(h, hipMemcpyAsync(h->out_h, h->out_d, bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->out_h.ptr, h->out_d, bytes, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    std::memcpy(dst, h->out_h, bytes);
+    std::memcpy(dst, h->out_h.ptr, bytes);
   }
   return TFG_OK;
 }
@@ -2165,20 +2146,21 @@ extern "C" void tfg_update_timing(double* out) {
 #endif
 
 namespace {
-// Wait for the workgroups' release flags of a tfg_update launch (a few
-// microseconds sooner than a stream synchronisation); after ~2 ms fall back to
-// the stream wait, which also reports a failed launch.
-int wait_flags(tfg_handle* h, size_t flag_off, int blocks, uint32_t seq) {
-  const volatile uint32_t* fl = reinterpret_cast<const volatile uint32_t*>(h->io_h + flag_off);
+// Wait until the `blocks` workgroups of a tfg_update / tfg_update_many launch
+// on `stream` have each stored `seq` to their release flag in the mapped block
+// (a few microseconds sooner than a stream synchronisation); after ~2 ms fall
+// back to the stream wait, which also reports a failed launch.  h (may be
+// null) takes the error.
+int wait_flags(tfg_handle* h, const char* flags, int blocks, uint32_t seq, hipStream_t stream) {
+  const volatile uint32_t* fl = reinterpret_cast<const volatile uint32_t*>(flags);
   const auto t0 = std::chrono::steady_clock::now();
-  bool done = false;
-  for (int64_t spins = 0; !done; ++spins) {
-    done = true;
-    for (int b = 0; b < blocks && done; ++b) done = fl[b] == seq;
-    if (!done && (spins & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
+  int done = 0;
+  for (int64_t spins = 0; done < blocks; ++spins) {
+    while (done < blocks && fl[done] == seq) ++done;
+    if (done < blocks && (spins & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
   }
-  if (done) std::atomic_thread_fence(std::memory_order_acquire);
-  else HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (done == blocks) std::atomic_thread_fence(std::memory_order_acquire);
+  else HIPCHK(h, hipStreamSynchronize(stream));
   return TFG_OK;
 }
 }  // namespace
@@ -2207,54 +2189,44 @@ int tfg_update(tfg_handle* h, int frame, const void* src, int src_dtype, const t
   const int blocks = fused_blocks(h);
   const size_t flag_off = (out_off + out_b + 255) & ~(size_t)255;
   const size_t total = flag_off + (size_t)blocks * 4;
-  if (h->io_cap < total) {
+  if (h->io.mem.cap < total) {
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->io_h) HIPCHK(h, hipHostFree(h->io_h));
-    h->io_h = h->io_d = nullptr;
-    h->io_cap = 0;
-    HIPCHK(h, hipHostMalloc((void**)&h->io_h, total, hipHostMallocMapped | hipHostMallocCoherent));
-    std::memset(h->io_h, 0, total);  // padding cells read zeros; flags start at 0
-    HIPCHK(h, hipHostGetDevicePointer((void**)&h->io_d, h->io_h, 0));
-    h->io_cap = total;
-    h->io_seq = 0;
+    HIPCHK(h, h->io.reserve(total));  // zeroed: padding cells read zeros, flags start at 0
   }
-  // BMI order (P_air, Hum_sp, P, T_air, uz) -> frame fields, converted to the engine type
-  static const int map[5] = {F_PA, F_Q, F_P, F_T, F_UZ};
+  char* const io_h = h->io.host();
+  char* const io_d = h->io.dev;
+  // the step's outputs and flags in the block; its inputs (IoArgs::in) only where k_fused reads them there
+  IoArgs io;
+  io.out = reinterpret_cast<double*>(io_d + out_off);
+  io.flag = reinterpret_cast<uint32_t*>(io_d + flag_off);
+  io.seq = h->io.next_seq();
+  auto unpack = [&] {  // the block's outputs into dst
+    const double* oh = reinterpret_cast<const double*>(io_h + out_off);
+    if (dst_dtype == TFG_F64) std::memcpy(dst, oh, out_b);
+    else for (int64_t i = 0; i < 8 * n; ++i) static_cast<float*>(dst)[i] = (float)oh[i];
+  };
   if (h->engine == TFG_F64 && n == 1) {
     // one catchment (NextGen's per-catchment model): k_cell, inputs and
     // uniforms as kernel arguments, one workgroup of four waves
     CellIo cio;
     cio.u = *u;
     for (int f = 0; f < 5; ++f)
-      cio.in[map[f]] = src_dtype == TFG_F64 ? static_cast<const double*>(src)[f] : (double)static_cast<const float*>(src)[f];
-    KArgs a;
-    a.p = h->dp;
-    a.K = 1;
-    a.n_catch = h->n_catch;
-    a.n = h->n;
-    a.n_pad = h->n_pad;
-    a.n_step = h->n_pad;
-    a.io_in = nullptr;
-    a.io_out = reinterpret_cast<double*>(h->io_d + out_off);
-    a.io_flag = reinterpret_cast<uint32_t*>(h->io_d + flag_off);
-    a.io_seq = ++h->io_seq == 0 ? ++h->io_seq : h->io_seq;  // never 0, the initial flag value
+      cio.in[kBmiToPlane[f]] = src_dtype == TFG_F64 ? static_cast<const double*>(src)[f] : (double)static_cast<const float*>(src)[f];
     TFG_TSTAMP(t_c0);
     TFG_TACC(0, t_in0, t_c0);
     if (int rc = prepare_steps(h)) return rc;
-    hipLaunchKernelGGL(k_cell, 1, 64 * tfg::kCellWaves, 0, h->stream, a, cio, reinterpret_cast<const double*>(h->geo), h->catch_id,
-                       h->st, h->tot, h->ring, static_cast<double*>(h->forc), static_cast<double*>(h->hist), h->slab,
-                       h->qc_on ? static_cast<const double*>(h->qc) : nullptr, h->depths_derived ? 0 : 1);
+    hipLaunchKernelGGL(k_cell, 1, 64 * tfg::kCellWaves, 0, h->stream, step_args(h, 1, io), cio, (const double*)h->geo.ptr,
+                       h->catch_id, h->st, h->tot, h->ring, (double*)h->forc.ptr, (double*)h->hist.ptr, h->slab,
+                       h->qc_on ? (const double*)h->qc.ptr : nullptr, h->depths_derived ? 0 : 1);
     HIPCHK(h, hipGetLastError());
     h->depths_derived = true;
     h->last_hist = u->hist;
     TFG_TSTAMP(t_c1);
     TFG_TACC(1, t_c0, t_c1);
-    if (int rc = wait_flags(h, flag_off, 1, a.io_seq)) return rc;
+    if (int rc = wait_flags(h, io_h + flag_off, 1, io.seq, h->stream)) return rc;
     TFG_TSTAMP(t_c2);
     TFG_TACC(2, t_c1, t_c2);
-    const double* oh = reinterpret_cast<const double*>(h->io_h + out_off);
-    if (dst_dtype == TFG_F64) std::memcpy(dst, oh, out_b);
-    else for (int64_t i = 0; i < 8; ++i) static_cast<float*>(dst)[i] = (float)oh[i];
+    unpack();
     TFG_TSTAMP(t_c3);
     TFG_TACC(3, t_c2, t_c3);
 #ifdef TFG_UPDATE_TIMING
@@ -2262,44 +2234,33 @@ int tfg_update(tfg_handle* h, int frame, const void* src, int src_dtype, const t
 #endif
     return TFG_OK;
   }
-  for (int f = 0; f < 5; ++f) {
-    char* o = h->io_h + (size_t)map[f] * np * h->rsz;
-    if (src_dtype == TFG_F64) {
-      const double* sv = static_cast<const double*>(src) + (size_t)f * n;
-      if (h->engine == TFG_F32) for (int64_t i = 0; i < n; ++i) reinterpret_cast<float*>(o)[i] = (float)sv[i];
-      else std::memcpy(o, sv, (size_t)n * 8);
-    } else {
-      const float* sv = static_cast<const float*>(src) + (size_t)f * n;
-      if (h->engine == TFG_F32) std::memcpy(o, sv, (size_t)n * 4);
-      else for (int64_t i = 0; i < n; ++i) reinterpret_cast<double*>(o)[i] = (double)sv[i];
-    }
-  }
-  std::memcpy(h->io_h + u_off, u, sizeof(tfg_uniforms));
-  step_table(h, u, 1, reinterpret_cast<StepAddr*>(h->io_h + u_off + sizeof(tfg_uniforms)), true);
-  IoArgs io;
+  // BMI order -> the frame's planes, converted to the engine type
+  by_types(h->engine, src_dtype, [&](auto r, auto s) {
+    using R = typename decltype(r)::type;
+    using S = typename decltype(s)::type;
+    for (int f = 0; f < 5; ++f)
+      std::copy_n(static_cast<const S*>(src) + (size_t)f * n, n, reinterpret_cast<R*>(io_h) + (size_t)kBmiToPlane[f] * np);
+  });
+  std::memcpy(io_h + u_off, u, sizeof(tfg_uniforms));
+  step_table(h, u, 1, reinterpret_cast<StepAddr*>(io_h + u_off + sizeof(tfg_uniforms)), true);
   if (h->engine == TFG_F32) {  // finite-data status of the step's inputs, as the kernel reads them
     io.in_state = kOk;
     for (int f = 0; f < 5; ++f)
-      if (host_finite(reinterpret_cast<const float*>(h->io_h + (size_t)map[f] * np * h->rsz), n) != kOk) io.in_state = kDirty;
+      if (host_finite_as_f32(reinterpret_cast<const float*>(io_h + (size_t)kBmiToPlane[f] * np * h->rsz), n) != kOk) io.in_state = kDirty;
   }
   TFG_TSTAMP(t_in1);
   TFG_TACC(0, t_in0, t_in1);
-  io.in = h->io_d;
-  io.out = reinterpret_cast<double*>(h->io_d + out_off);
-  io.flag = reinterpret_cast<uint32_t*>(h->io_d + flag_off);
-  io.seq = ++h->io_seq == 0 ? ++h->io_seq : h->io_seq;  // never 0, the initial flag value
-  const tfg_uniforms* d_u = reinterpret_cast<const tfg_uniforms*>(h->io_d + u_off);
+  io.in = io_d;
+  const tfg_uniforms* d_u = reinterpret_cast<const tfg_uniforms*>(io_d + u_off);
   if (int rc = launch_steps(h, d_u, table_of(d_u, 1), nullptr, u, 1, io)) return rc;
   if (h->engine == TFG_F32)  // the kernel stored the inputs into the frame
     std::fill_n(h->plane_state.begin() + (size_t)frame * kNumForc, kNumForc, io.in_state);
   TFG_TSTAMP(t_l1);
   TFG_TACC(1, t_in1, t_l1);
-  if (int rc = wait_flags(h, flag_off, blocks, io.seq)) return rc;
+  if (int rc = wait_flags(h, io_h + flag_off, blocks, io.seq, h->stream)) return rc;
   TFG_TSTAMP(t_w1);
   TFG_TACC(2, t_l1, t_w1);
-  const double* oh = reinterpret_cast<const double*>(h->io_h + out_off);
-  if (dst_dtype == TFG_F64) std::memcpy(dst, oh, out_b);
-  else for (int64_t i = 0; i < 8 * n; ++i) static_cast<float*>(dst)[i] = (float)oh[i];
+  unpack();
   TFG_TSTAMP(t_o1);
   TFG_TACC(3, t_w1, t_o1);
 #ifdef TFG_UPDATE_TIMING
@@ -2314,13 +2275,11 @@ namespace {
 // synchronous, so one block per device serves every call, under its mutex.
 struct ManyBlock {
   std::mutex mu;
-  char* h = nullptr;
-  char* d = nullptr;
-  size_t cap = 0;
-  uint32_t seq = 0;
+  MappedBlock io;
 };
 constexpr int kMaxDevices = 64;
-ManyBlock g_many[kMaxDevices];
+// never destroyed (as tfg_shared_stream's streams): no HIP call during static destruction
+ManyBlock* const g_many = new ManyBlock[kMaxDevices];
 }  // namespace
 
 int tfg_update_many(tfg_handle* const* hs, int m, const double* const* src, const tfg_uniforms* const* u,
@@ -2354,58 +2313,41 @@ int tfg_update_many(tfg_handle* const* hs, int m, const double* const* src, cons
   const size_t out_off = (job_b + 255) & ~(size_t)255;
   const size_t flag_off = (out_off + (size_t)m * 64 + 255) & ~(size_t)255;
   const size_t total = flag_off + (size_t)m * 4;
-  if (B.cap < total) {
-    const size_t want = std::max(total, B.cap * 2);
-    if (B.h) HIPCHK(nullptr, hipHostFree(B.h));
-    B.h = B.d = nullptr;
-    B.cap = 0;
-    HIPCHK(nullptr, hipHostMalloc((void**)&B.h, want, hipHostMallocMapped | hipHostMallocCoherent));
-    std::memset(B.h, 0, want);
-    HIPCHK(nullptr, hipHostGetDevicePointer((void**)&B.d, B.h, 0));
-    B.cap = want;
-    B.seq = 0;
-  }
-  CellJob* jobs = reinterpret_cast<CellJob*>(B.h);
-  static const int map[5] = {F_PA, F_Q, F_P, F_T, F_UZ};  // BMI order -> device frame order
+  if (B.io.mem.cap < total)  // calls are synchronous: no launch still uses the block
+    HIPCHK(nullptr, B.io.reserve(std::max(total, B.io.mem.cap * 2)));
+  char* const io_h = B.io.host();
+  char* const io_d = B.io.dev;
+  CellJob* jobs = reinterpret_cast<CellJob*>(io_h);
   for (int i = 0; i < m; ++i) {
     tfg_handle* h = hs[i];
     if (int rc = prepare_steps(h)) return fail(nullptr, rc, "tfg_update_many: " + h->err);
     CellJob& j = jobs[i];
     j.p = h->dp;
     j.u = *u[i];
-    for (int f = 0; f < 5; ++f) j.in[map[f]] = src[i][f];
-    j.geo = reinterpret_cast<const double*>(h->geo);
+    for (int f = 0; f < 5; ++f) j.in[kBmiToPlane[f]] = src[i][f];
+    j.geo = (const double*)h->geo.ptr;
     j.catch_id = h->catch_id;
     j.st = h->st;
     j.tot = h->tot;
     j.ring = h->ring;
-    j.forc = static_cast<double*>(h->forc);
-    j.hist = static_cast<double*>(h->hist);
+    j.forc = (double*)h->forc.ptr;
+    j.hist = (double*)h->hist.ptr;
     j.slab = h->slab;
-    j.qc = h->qc_on ? static_cast<const double*>(h->qc) : nullptr;
+    j.qc = h->qc_on ? (const double*)h->qc.ptr : nullptr;
     j.n_pad = h->n_pad;
     j.read_depths = h->depths_derived ? 0 : 1;
     j.pad_ = 0;
   }
-  const uint32_t seq = ++B.seq == 0 ? ++B.seq : B.seq;  // never 0, the initial flag value
-  hipLaunchKernelGGL(k_cell_many, m, 64 * tfg::kCellWaves, 0, h0->stream, reinterpret_cast<const CellJob*>(B.d),
-                     reinterpret_cast<double*>(B.d + out_off), reinterpret_cast<uint32_t*>(B.d + flag_off), seq);
+  const uint32_t seq = B.io.next_seq();
+  hipLaunchKernelGGL(k_cell_many, m, 64 * tfg::kCellWaves, 0, h0->stream, reinterpret_cast<const CellJob*>(io_d),
+                     reinterpret_cast<double*>(io_d + out_off), reinterpret_cast<uint32_t*>(io_d + flag_off), seq);
   HIPCHK(nullptr, hipGetLastError());
   for (int i = 0; i < m; ++i) {
     hs[i]->depths_derived = true;
     hs[i]->last_hist = u[i]->hist;
   }
-  // wait for every workgroup's release flag (a stream synchronisation after ~2 ms)
-  const volatile uint32_t* fl = reinterpret_cast<const volatile uint32_t*>(B.h + flag_off);
-  const auto t0 = std::chrono::steady_clock::now();
-  int done = 0;
-  for (int64_t spins = 0; done < m; ++spins) {
-    while (done < m && fl[done] == seq) ++done;
-    if (done < m && (spins & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
-  }
-  if (done == m) std::atomic_thread_fence(std::memory_order_acquire);
-  else HIPCHK(nullptr, hipStreamSynchronize(h0->stream));
-  const double* oh = reinterpret_cast<const double*>(B.h + out_off);
+  if (int rc = wait_flags(nullptr, io_h + flag_off, m, seq, h0->stream)) return rc;
+  const double* oh = reinterpret_cast<const double*>(io_h + out_off);
   for (int i = 0; i < m; ++i) std::memcpy(dst[i], oh + (size_t)i * 8, 64);
   return TFG_OK;
 }
@@ -2418,9 +2360,9 @@ int tfg_terrain_from_dem(tfg_handle* h, double dx, double dy, const void* halo_n
   if (halo_dtype != TFG_F32 && halo_dtype != TFG_F64) return fail(h, TFG_ERR_ARG, "halo dtype must be TFG_F32/TFG_F64");
   HIPCHK(h, hipSetDevice(h->device));
   const int64_t nx = h->nx, ny = h->ny;
-  if (!h->halo) HIPCHK(h, hipMalloc((void**)&h->halo, (size_t)2 * nx * 8));
+  HIPCHK(h, h->halo.reserve((size_t)2 * nx * 8));
   const size_t rs = h->rsz;
-  const char* el = static_cast<const char*>(h->stat);  // TFG_ST_ELEV plane
+  const char* el = h->stat.bytes();  // TFG_ST_ELEV plane
   // a missing halo replicates the shard's own edge row (domain boundary)
   const void* src[2] = {halo_north, halo_south};
   for (int k = 0; k < 2; ++k) {
@@ -2433,13 +2375,12 @@ int tfg_terrain_from_dem(tfg_handle* h, double dx, double dy, const void* halo_n
       if (rc) return rc;
     }
   }
-  char* st = static_cast<char*>(h->stat);
-  if (h->engine == TFG_F32)
-    hipLaunchKernelGGL((k_terrain<float>), grid_for(h->n), 256, 0, h->stream, (const float*)st, h->halo,
-                       (float*)(st + h->n_pad * rs), (float*)(st + 2 * h->n_pad * rs), ny, nx, 1.0 / (8.0 * dx), 1.0 / (8.0 * dy));
-  else
-    hipLaunchKernelGGL((k_terrain<double>), grid_for(h->n), 256, 0, h->stream, (const double*)st, h->halo,
-                       (double*)(st + h->n_pad * rs), (double*)(st + 2 * h->n_pad * rs), ny, nx, 1.0 / (8.0 * dx), 1.0 / (8.0 * dy));
+  char* st = h->stat.bytes();
+  by_type(h->engine, [&](auto t) {
+    using R = typename decltype(t)::type;
+    hipLaunchKernelGGL((k_terrain<R>), grid_for(h->n), 256, 0, h->stream, (const R*)st, h->halo, (R*)(st + h->n_pad * rs),
+                       (R*)(st + 2 * h->n_pad * rs), ny, nx, 1.0 / (8.0 * dx), 1.0 / (8.0 * dy));
+  });
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->geo_dirty = true;
@@ -2453,7 +2394,7 @@ namespace {
 int flow_setup(tfg_handle* h, const double* hn, const double* hs, int on_dev, FlowGrid& g) {
   if (!h->initialised) return fail(h, TFG_ERR_STATE, "tfg_init_state() has not been called");
   const int64_t nx = h->nx;
-  if (!h->flow_halo) HIPCHK(h, hipMalloc((void**)&h->flow_halo, (size_t)4 * nx * 8));
+  HIPCHK(h, h->flow_halo.reserve((size_t)4 * nx * 8));
   if (hn) HIPCHK(h, hipMemcpyAsync(h->flow_halo, hn, (size_t)2 * nx * 8, on_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
   if (hs) HIPCHK(h, hipMemcpyAsync(h->flow_halo + 2 * nx, hs, (size_t)2 * nx * 8, on_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
   g.elev = h->stat;
@@ -2474,12 +2415,11 @@ int tfg_ice_flow_edges(tfg_handle* h, double* first, double* last, int on_device
   FlowGrid g;
   if (int rc = flow_setup(h, nullptr, nullptr, 0, g)) return rc;
   const int64_t nx = h->nx;
-  if (!h->flow_edges) HIPCHK(h, hipMalloc((void**)&h->flow_edges, (size_t)4 * nx * 8));
-  const int gb = grid_for(nx);
-  if (h->engine == TFG_F32)
-    hipLaunchKernelGGL((k_ice_flow_edges<float>), gb, 256, 0, h->stream, g, h->flow_edges, h->flow_edges + 2 * nx);
-  else
-    hipLaunchKernelGGL((k_ice_flow_edges<double>), gb, 256, 0, h->stream, g, h->flow_edges, h->flow_edges + 2 * nx);
+  HIPCHK(h, h->flow_edges.reserve((size_t)4 * nx * 8));
+  by_type(h->engine, [&](auto t) {
+    using R = typename decltype(t)::type;
+    hipLaunchKernelGGL((k_ice_flow_edges<R>), grid_for(nx), 256, 0, h->stream, g, h->flow_edges, h->flow_edges + 2 * nx);
+  });
   HIPCHK(h, hipGetLastError());
   const hipMemcpyKind k = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
   HIPCHK(h, hipMemcpyAsync(first, h->flow_edges, (size_t)2 * nx * 8, k, h->stream));
@@ -2501,11 +2441,11 @@ int tfg_ice_flow_dmax(tfg_handle* h, double dx, double dy, const double* halo_no
   const int64_t gb = (int64_t)fgrid.x * fgrid.y;
   const FlowTiles ft = flow_tiles(h->nx, (int)fgrid.y);
   const FlowK fk = flow_constants(1.0, dx, dy, h->dp.wi, h->flow_gamma);  // dt unused by the bound
-  if (!h->flow_red) HIPCHK(h, hipMalloc((void**)&h->flow_red, (size_t)gb * 8));  // the grid never changes
-  if (h->engine == TFG_F32)
-    hipLaunchKernelGGL((k_ice_flow<float, true>), flow_blocks(ft), kFlowTX, 0, h->stream, g, fk, h->flow_red, 0, 1, nullptr, ft);
-  else
-    hipLaunchKernelGGL((k_ice_flow<double, true>), flow_blocks(ft), kFlowTX, 0, h->stream, g, fk, h->flow_red, 0, 1, nullptr, ft);
+  HIPCHK(h, h->flow_red.reserve((size_t)gb * 8));  // the grid never changes
+  by_type(h->engine, [&](auto t) {
+    using R = typename decltype(t)::type;
+    hipLaunchKernelGGL((k_ice_flow<R, true>), flow_blocks(ft), kFlowTX, 0, h->stream, g, fk, h->flow_red, 0, 1, nullptr, ft);
+  });
   HIPCHK(h, hipGetLastError());
   std::vector<double> bm(gb);
   HIPCHK(h, hipMemcpyAsync(bm.data(), h->flow_red, (size_t)gb * 8, hipMemcpyDeviceToHost, h->stream));
@@ -2528,7 +2468,7 @@ int tfg_ice_flow_step(tfg_handle* h, double dt_years, double dx, double dy, cons
   HIPCHK(h, hipSetDevice(h->device));
   FlowGrid g;
   if (int rc = flow_setup(h, halo_north, halo_south, halo_on_device, g)) return rc;
-  if (!h->wtmp) HIPCHK(h, hipMalloc((void**)&h->wtmp, (size_t)h->n_pad * 8));
+  HIPCHK(h, h->wtmp.reserve((size_t)h->n_pad * 8));
   const int64_t strips = (h->ny + kFlowRows - 1) / kFlowRows;
   if (strips > 65535) return fail(h, TFG_ERR_ARG, "ice flow: too many rows for one shard");
   const FlowK fk = flow_constants(dt_years, dx, dy, h->dp.wi, h->flow_gamma);
@@ -2542,10 +2482,10 @@ int tfg_ice_flow_step(tfg_handle* h, double dt_years, double dx, double dy, cons
   double* ice = h->st + S_HICE * h->n_pad;
   if (count > 0) {
     const FlowTiles ft = flow_tiles(h->nx, count);
-    if (h->engine == TFG_F32)
-      hipLaunchKernelGGL((k_ice_flow<float, false>), flow_blocks(ft), kFlowTX, 0, h->stream, g, fk, h->wtmp, first, step, ice, ft);
-    else
-      hipLaunchKernelGGL((k_ice_flow<double, false>), flow_blocks(ft), kFlowTX, 0, h->stream, g, fk, h->wtmp, first, step, ice, ft);
+    by_type(h->engine, [&](auto t) {
+      using R = typename decltype(t)::type;
+      hipLaunchKernelGGL((k_ice_flow<R, false>), flow_blocks(ft), kFlowTX, 0, h->stream, g, fk, h->wtmp, first, step, ice, ft);
+    });
     HIPCHK(h, hipGetLastError());
   }
   if (part == TFG_FLOW_INTERIOR) return TFG_OK;  // queued; the edges part commits
@@ -2562,7 +2502,7 @@ int tfg_ice_flow_run(tfg_handle* h, double dt_years, double dx, double dy, int n
   HIPCHK(h, hipSetDevice(h->device));
   FlowGrid g;
   if (int rc = flow_setup(h, nullptr, nullptr, 0, g)) return rc;
-  if (!h->wtmp) HIPCHK(h, hipMalloc((void**)&h->wtmp, (size_t)h->n_pad * 8));
+  HIPCHK(h, h->wtmp.reserve((size_t)h->n_pad * 8));
   const int64_t strips = (h->ny + kFlowRows - 1) / kFlowRows;
   if (strips > 65535) return fail(h, TFG_ERR_ARG, "ice flow: too many rows for one shard");
   const FlowK fk = flow_constants(dt_years / n_sub, dx, dy, h->dp.wi, h->flow_gamma);
@@ -2576,12 +2516,11 @@ int tfg_ice_flow_run(tfg_handle* h, double dt_years, double dx, double dy, int n
     const bool to_state = (k & 1) != 0;
     g.iwe = to_state ? h->wtmp : plane;
     double* dst = to_state ? plane : h->wtmp;
-    if (h->engine == TFG_F32)
-      hipLaunchKernelGGL((k_ice_flow<float, false>), flow_blocks(ft), kFlowTX, 0, h->stream, g, fk, dst, 0, 1,
+    by_type(h->engine, [&](auto t) {
+      using R = typename decltype(t)::type;
+      hipLaunchKernelGGL((k_ice_flow<R, false>), flow_blocks(ft), kFlowTX, 0, h->stream, g, fk, dst, 0, 1,
                          to_state ? ice : nullptr, ft);
-    else
-      hipLaunchKernelGGL((k_ice_flow<double, false>), flow_blocks(ft), kFlowTX, 0, h->stream, g, fk, dst, 0, 1,
-                         to_state ? ice : nullptr, ft);
+    });
     HIPCHK(h, hipGetLastError());
   }
   if (n_sub & 1)
@@ -2596,7 +2535,7 @@ namespace {
 int cond_setup(tfg_handle* h, const double* hn, const double* hs, int on_dev, tfg::CondGrid& g) {
   if (!h->initialised) return fail(h, TFG_ERR_STATE, "tfg_init_state() has not been called");
   const int64_t nx = h->nx, np = h->n_pad;
-  if (!h->cond_halo) HIPCHK(h, hipMalloc((void**)&h->cond_halo, (size_t)8 * nx * 8));
+  HIPCHK(h, h->cond_halo.reserve((size_t)8 * nx * 8));
   const hipMemcpyKind k = on_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
   if (hn) HIPCHK(h, hipMemcpyAsync(h->cond_halo, hn, (size_t)4 * nx * 8, k, h->stream));
   if (hs) HIPCHK(h, hipMemcpyAsync(h->cond_halo + 4 * nx, hs, (size_t)4 * nx * 8, k, h->stream));
@@ -2624,7 +2563,7 @@ int tfg_conduction_edges(tfg_handle* h, double* first, double* last, int on_devi
   tfg::CondGrid g;
   if (int rc = cond_setup(h, nullptr, nullptr, 0, g)) return rc;
   const int64_t nx = h->nx;
-  if (!h->cond_edges) HIPCHK(h, hipMalloc((void**)&h->cond_edges, (size_t)8 * nx * 8));
+  HIPCHK(h, h->cond_edges.reserve((size_t)8 * nx * 8));
   hipLaunchKernelGGL(tfg::k_conduction_edges, grid_for(nx), 256, 0, h->stream, g, h->cond_edges, h->cond_edges + 4 * nx);
   HIPCHK(h, hipGetLastError());
   const hipMemcpyKind k = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
@@ -2651,12 +2590,11 @@ int tfg_conduction_update(tfg_handle* h, double k_snow, double k_ice, double dx,
   if (int rc = cond_setup(h, halo_north, halo_south, halo_on_device, g)) return rc;
   const tfg::CondK K = {k_snow / (dx * dx), k_snow / (dy * dy), k_ice * h->h_active / (dx * dx),
                         k_ice * h->h_active / (dy * dy), q_ground};
-  if (h->engine == TFG_F32)
-    hipLaunchKernelGGL((tfg::k_conduction<float>), (unsigned)(8 * per_xcd), tfg::kCondTX, 0, h->stream, g, K,
-                       (float*)h->qc, (int)gx, (int)strips, (int)per_xcd);
-  else
-    hipLaunchKernelGGL((tfg::k_conduction<double>), (unsigned)(8 * per_xcd), tfg::kCondTX, 0, h->stream, g, K,
-                       (double*)h->qc, (int)gx, (int)strips, (int)per_xcd);
+  by_type(h->engine, [&](auto t) {
+    using R = typename decltype(t)::type;
+    hipLaunchKernelGGL((tfg::k_conduction<R>), (unsigned)(8 * per_xcd), tfg::kCondTX, 0, h->stream, g, K, (R*)h->qc.ptr,
+                       (int)gx, (int)strips, (int)per_xcd);
+  });
   HIPCHK(h, hipGetLastError());
   // the halo rows are the caller's: finish reading them before returning
   if (halo_north || halo_south) HIPCHK(h, hipStreamSynchronize(h->stream));
