@@ -317,6 +317,44 @@ int tfg_reset_diag(tfg_handle* h);
  * cells -- with TFG_OUT_M_TOTAL, times da_m2, a hydrograph per catchment. */
 int tfg_catchment_series(tfg_handle* h, int field, int hist0, int nslots, double* out, int out_on_device);
 
+/* Per-cell time aggregates of one output field over history slots, folded on
+ * the device.  For every cell i < ny*nx, with v_j = field[slot (hist0 + j) %
+ * hist_depth][i] in the engine's element type, j = 0 .. nslots-1 in that
+ * order (a left fold: sum is ((acc + v_0) + v_1) + ..., the others alike):
+ *   sum   [n] fp64          sum  = sum + (double)v_j             from +0.0
+ *   vmax  [n] engine type   vmax = max(vmax, v_j)                from v_0
+ *   vmin  [n] engine type   vmin = min(vmin, v_j)                from v_0
+ *   count [n] int32         count += ((double)v_j > threshold)   from 0
+ * max and min propagate NaN as numpy's np.maximum / np.minimum do; a NaN value
+ * is never counted.  With init != 0 each accumulator starts from the value in
+ * the last column and its buffer is not read; with init == 0 it continues from
+ * what its buffer holds (which may itself be NaN).  No partial result of a
+ * batch of slots is formed and added afterwards, so a period accumulated over
+ * several calls equals one call over all its slots bit for bit, and both equal
+ * a numpy loop over the planes in step order bit for bit.
+ * A null pointer leaves that statistic out, at no cost; at least one is set.
+ * All four are device pointers on the handle's device, of exactly ny*nx
+ * elements with the natural alignment of their type (16-byte aligned buffers
+ * take the wider path); no element past the last is touched.  The buffers
+ * must not overlap each other or any engine memory; this is not checked.
+ * `field` is one of the six history fields (TFG_OUT_H_SNOW, _SM, _H_ICE, _IM,
+ * _M_TOTAL, _RH); 0 <= hist0 < hist_depth, 1 <= nslots <= hist_depth; the
+ * threshold is not NaN when count is set.  The call is queued on the handle's
+ * stream (after the second part of a split launch) without a host wait.
+ * Replaces: the per-step get_value loop of a caller of the reference that sums
+ * or inspects outputs over time (examples/run_topoflow_glacier.py:64-115), for
+ * every cell of a grid: daily or seasonal melt and runoff depth, mean and peak
+ * snow depth, hours with melt, snow-cover duration. */
+typedef struct tfg_cell_stats {
+  double*  sum;     /* [n] fp64, or NULL                                   */
+  void*    vmax;    /* [n] engine element type, or NULL                    */
+  void*    vmin;    /* [n] engine element type, or NULL                    */
+  int32_t* count;   /* [n], or NULL: slots whose value > threshold         */
+  double   threshold;
+} tfg_cell_stats;
+int tfg_cell_aggregate(tfg_handle* h, int field, int hist0, int nslots,
+                       const tfg_cell_stats* acc, int init);
+
 /* Wait for all work queued on the handle's stream. */
 int tfg_sync(tfg_handle* h);
 

@@ -496,6 +496,7 @@ __global__ void k_terrain(const R* __restrict__ elev, const double* __restrict__
 
 #include "tfg_flow.hpp"  // the optional ice-flow kernels (tfg_ice_flow_*)
 #include "tfg_series.hpp"  // per-catchment sums of history planes (tfg_catchment_series)
+#include "tfg_aggregate.hpp"  // per-cell time aggregates of history planes (tfg_cell_aggregate)
 #include "tfg_forcing.hpp"  // per-catchment forcing spread over the grid (tfg_set_catchment_forcing)
 
 // tfg_set_inputs / tfg_get_outputs: the per-step BMI traffic of one call each.
@@ -1888,6 +1889,34 @@ int tfg_catchment_series(tfg_handle* h, int field, int hist0, int nslots, double
     HIPCHK(h, hipMemcpyAsync(out, dout, (size_t)nslots * h->n_catch * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
   }
+  return TFG_OK;
+}
+
+int tfg_cell_aggregate(tfg_handle* h, int field, int hist0, int nslots, const tfg_cell_stats* acc, int init) {
+  if (int rc_ = api_sync(h)) return rc_;  // after a split launch's second part
+  if (!h) return fail(nullptr, TFG_ERR_ARG, "null handle");
+  if (!acc) return fail(h, TFG_ERR_ARG, "cell aggregate: null acc");
+  if (!acc->sum && !acc->vmax && !acc->vmin && !acc->count) return fail(h, TFG_ERR_ARG, "cell aggregate: no statistic requested");
+  if (!is_hist_field(field))
+    return fail(h, TFG_ERR_ARG, "cell aggregate: field " + std::to_string(field) +
+                                    " is not a history field (h_snow, SM, h_ice, IM, M_total, RH)");
+  if (hist0 < 0 || hist0 >= h->hist_depth) return fail(h, TFG_ERR_ARG, "cell aggregate: first history slot out of range");
+  if (nslots < 1 || nslots > h->hist_depth) return fail(h, TFG_ERR_ARG, "cell aggregate: slot count outside 1..hist_depth");
+  if (acc->count && acc->threshold != acc->threshold) return fail(h, TFG_ERR_ARG, "cell aggregate: NaN threshold");
+  HIPCHK(h, hipSetDevice(h->device));
+  int fdt = 0;
+  const void* plane = field_ptr(h, field, 0, &fdt);  // slot 0's plane of the field, engine type
+  const int64_t stride = (int64_t)kNumHist * h->n_pad;
+  auto aligned = [](const void* p, int bit) { return p && ((uintptr_t)p & 15) == 0 ? bit : 0; };
+  const int vec = aligned(acc->sum, kAggVecSum) | aligned(acc->vmax, kAggVecMax) | aligned(acc->vmin, kAggVecMin) |
+                  aligned(acc->count, kAggVecCount);
+  by_type(h->engine, [&](auto t) {
+    using R = typename decltype(t)::type;
+    hipLaunchKernelGGL(k_cell_aggregate<R>, aggregate_blocks(h->n, 16 / (int)sizeof(R)), kBlock, 0, h->stream,
+                       (const R*)plane, stride, h->hist_depth, hist0, nslots, h->n, acc->sum, (R*)acc->vmax, (R*)acc->vmin,
+                       acc->count, acc->threshold, init != 0 ? 1 : 0, vec);
+  });
+  HIPCHK(h, hipGetLastError());
   return TFG_OK;
 }
 

@@ -60,6 +60,12 @@ class TfgDownscale(ctypes.Structure):
                 ("pressure", ctypes.c_int32), ("pad", ctypes.c_int32)]
 
 
+class TfgCellStats(ctypes.Structure):
+    """tfg_cell_stats: the accumulators of tfg_cell_aggregate (device pointers, or None)."""
+    _fields_ = [("sum", ctypes.c_void_p), ("vmax", ctypes.c_void_p), ("vmin", ctypes.c_void_p),
+                ("count", ctypes.c_void_p), ("threshold", ctypes.c_double)]
+
+
 # tfg_uniforms, one record per time step (numpy structured dtype, C layout)
 _U_D = ["th", "omega_th", "cos_wth", "sin_wth", "sin_d", "cos_d", "tan_d", "isc_e0", "m_opt",
         "k_et_flat", "flat_sr", "flat_ss"]
@@ -114,6 +120,7 @@ def load() -> ctypes.CDLL:
         "tfg_get_diag": ([vp, dp, i32], i32),
         "tfg_reset_diag": ([vp], i32),
         "tfg_catchment_series": ([vp, i32, i32, i32, vp, i32], i32),
+        "tfg_cell_aggregate": ([vp, i32, i32, i32, ctypes.POINTER(TfgCellStats), i32], i32),
         "tfg_sync": ([vp], i32),
         "tfg_fill_synthetic": ([vp, ctypes.c_uint64, i64, i64, ctypes.POINTER(ctypes.c_float), i32], i32),
         "tfg_last_error": ([vp], ctypes.c_char_p),
@@ -307,5 +314,5 @@ def exported_symbols() -> list[str]:
         "tfg_fill_synthetic", "tfg_last_error", "tfg_terrain_from_dem", "tfg_ice_flow_edges", "tfg_ice_flow_dmax", "tfg_ice_flow_step", "tfg_ice_flow_run", "tfg_set_inputs", "tfg_get_outputs",
         "tfg_update", "tfg_update_many", "tfg_conduction_edges", "tfg_conduction_update", "tfg_conduction_off",
         "tfg_nan_safe_launches", "tfg_set_step_form", "tfg_set_flux", "tfg_set_split", "tfg_join", "tfg_get_split",
-        "tfg_selftest_powers", "tfg_catchment_series", "tfg_set_catchment_forcing",
+        "tfg_selftest_powers", "tfg_catchment_series", "tfg_set_catchment_forcing", "tfg_cell_aggregate",
     ) if hasattr(L, n)]

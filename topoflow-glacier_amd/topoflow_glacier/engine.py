@@ -11,6 +11,7 @@ All arithmetic happens in the HIP kernels; this class never computes physics.
 
 from __future__ import annotations
 
+import builtins
 import ctypes
 import os
 
@@ -649,6 +650,59 @@ class GlacierEngine:
             res = np.where(cells > 0, res / np.maximum(cells, 1), 0.0)
         return res
 
+    def cell_aggregate(self, name: str, first: int | None = None, count: int | None = None, *, sum=None, max=None,
+                       min=None, above=None, threshold: float = 0.0, init: bool = False) -> None:
+        """Fold `count` consecutive history slots of an output field, from slot
+        `first` and following the ring, into per-cell accumulators on the
+        device (tfg_cell_aggregate; the planes stay there).  In slot order,
+        with v the cell's value in a slot:
+
+            sum    float64         sum += float64(v)
+            max    engine dtype    np.maximum(max, v)    (NaN-propagating)
+            min    engine dtype    np.minimum(min, v)
+            above  int32           above += (float64(v) > threshold)
+
+        With init=True the accumulators start from +0.0, the first slot's
+        value (max, min) and 0, and are not read; otherwise they continue from
+        what they hold, and a period folded piece by piece equals one call
+        over all its slots bit for bit.  Defaults for `first` and `count`: the
+        slots of the last min(step_index, hist_depth) steps, in step order.
+
+        Each given accumulator is a torch CUDA tensor of n elements on the
+        engine's device, contiguous (a view at any element offset will do) and
+        not overlapping another; at least one is given.  The call is queued on
+        the engine's stream without a host wait, under get_field_device's
+        stream rules -- torch's current stream is drained first, and the
+        caller sync()s (or orders its stream after the engine's) before
+        reading."""
+        import torch
+
+        if count is None:
+            count = builtins.max(builtins.min(self.step_index, self.hist_depth), 1)  # max, min: arguments here
+        if first is None:
+            first = (self.step_index - count) % self.hist_depth if self.step_index else 0
+        first, count = int(first), int(count)
+        fid = nat.FIELD[name]
+        eng_dtype = {nat.F32: torch.float32, nat.F64: torch.float64}[self.dtype_code]
+        given = (("sum", sum, torch.float64), ("max", max, eng_dtype), ("min", min, eng_dtype), ("above", above, torch.int32))
+        if all(t is None for _, t, _ in given):
+            raise ValueError("cell_aggregate: give at least one of sum, max, min, above")
+        for what, t, dt in given:
+            if t is None:
+                continue
+            if not (getattr(t, "is_cuda", False) and t.device.index == self.device):
+                raise ValueError(f"{what}: need a CUDA tensor on cuda:{self.device}")
+            if t.dtype != dt:
+                raise ValueError(f"{what}: dtype {t.dtype}, need {dt}")
+            if t.numel() != self.n or not t.is_contiguous():
+                raise ValueError(f"{what}: need a contiguous tensor of {self.n} elements")
+        threshold = float(threshold)
+        if above is not None and threshold != threshold:
+            raise ValueError("cell_aggregate: the threshold of `above` is NaN")
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        acc = nat.TfgCellStats(ptr(sum), ptr(max), ptr(min), ptr(above), threshold)
+        torch.cuda.current_stream(self.torch_device).synchronize()  # the buffers may still be in use on torch's stream
+        self._chk(self.lib.tfg_cell_aggregate(self.h, fid, first, count, ctypes.byref(acc), 1 if init else 0))
 
 
 class UpdateBatch:

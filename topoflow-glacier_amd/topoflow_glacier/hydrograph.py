@@ -22,7 +22,8 @@ from .routing import boxcar_route
 __all__ = ["catchment_hydrographs", "forced_catchment_hydrographs"]
 
 
-def catchment_hydrographs(eng, nsteps: int, frames=None, group=None, taps: int = 20, on_block=None) -> dict:
+def catchment_hydrographs(eng, nsteps: int, frames=None, group=None, taps: int = 20, on_block=None,
+                          after_block=None) -> dict:
     """Advance `eng` (a GlacierEngine) by nsteps steps and return
     ``{"runoff": [nsteps][n_catch] m3 s-1, "routed": boxcar_route(runoff, taps)}``.
 
@@ -33,6 +34,11 @@ def catchment_hydrographs(eng, nsteps: int, frames=None, group=None, taps: int =
     on_block   on_block(k0, k1) is called before the block of steps k0..k1-1
                (relative to this call) is queued: the place to load the forcing
                frames those steps read
+    after_block  after_block(k0, k1, first) is called once the block's steps and
+               its series are queued, with the history slot `first` that step k0
+               wrote: the place to fold the same planes into per-cell aggregates
+               (aggregate.PeriodFolder.fold), so that hydrographs and cell maps
+               come out of one pass over the ring
     """
     import torch
 
@@ -50,6 +56,8 @@ def catchment_hydrographs(eng, nsteps: int, frames=None, group=None, taps: int =
         first = eng.step_index % depth  # the slot the block's first step writes
         eng.run(k1 - k0, frames=None if frames is None else frames[k0:k1])
         eng.catchment_series("M_total", first=first, count=k1 - k0, out=buf[k0:k1])
+        if after_block is not None:
+            after_block(k0, k1, first)
     eng.sync()
     runoff = buf.cpu().numpy() * float(eng.params.da_m2)
     from .sharding import allreduce_catchment_series
