@@ -232,6 +232,53 @@ typedef struct tfg_downscale {
 int tfg_set_catchment_forcing(tfg_handle* h, int frame0, int nframes, const double* table, int table_on_device,
                               const double* z_ref, const tfg_downscale* ds);
 
+/* Forcing frames from fields on a regular source grid far coarser (or finer)
+ * than the model's, interpolated onto the model grid on the device.  src is
+ * [nframes][5][gny][gnx] fp64, the five inputs in tfg_set_inputs order; source
+ * node (j, i) sits at source-grid coordinate (j, i).  For local cell (r, c),
+ * with R = row0 + r, all in fp64 without contraction and rounded once to the
+ * engine's type at the store:
+ *   y = y0 + sy R,  yc = min(max(y, 0), gny - 1)          (x alike, from c)
+ * The clamp comes first: outside the source grid the edge value is held.
+ *   bilinear: j0 = min(floor(yc), max(gny - 2, 0)), j1 = min(j0 + 1, gny - 1),
+ *     wy = yc - j0 (i0, i1, wx alike), and vertically first
+ *       west = a[j0][i0] + wy (a[j1][i0] - a[j0][i0])
+ *       east = a[j0][i1] + wy (a[j1][i1] - a[j0][i1])
+ *       v    = west + wx (east - west)
+ *   nearest:  v = a[floor(yc + 0.5)][floor(xc + 0.5)]       (ties go up)
+ * ds == NULL, or every term off: the cell's five values are the interpolated
+ * fields; z_src may then be NULL.  With a term on, they take the place of a
+ * catchment's table values in tfg_set_catchment_forcing's terms, and z_src
+ * [gny][gnx], the source grid's elevation interpolated by the same method,
+ * that of z_ref: dz = elev[i] - z.  z_src lives on the same side as src.
+ * A host source is copied into the pinned staging ring (src | z_src, one
+ * queued copy) and the call returns without waiting for the device; a device
+ * source is read in stream order.  A frame's planes are the same bit for bit
+ * whichever call, batch position or shard (row0) produced them.
+ * TFG_ERR_ARG (no frame is touched): null handle, src or g, frames outside
+ * 0 .. n_frames, gny or gnx < 1 or gny * gnx >= 2^29 (a field of 4 GiB or
+ * more), a method other than the two, a non-finite
+ * y0, x0, sy or sx, row0 < 0, tfg_set_catchment_forcing's checks of ds,
+ * z_src == NULL with a term on.  A NaN node reaches exactly the cells whose
+ * stencil (j0|j1 x i0|i1, or the nearest node) holds it, whatever its weight,
+ * in its own frame and variable, plus what the terms derive from it.
+ * No reference counterpart (one cell per catchment); the rule is restated in
+ * numpy by tests/regrid_ref.py. */
+#define TFG_REGRID_NEAREST  0
+#define TFG_REGRID_BILINEAR 1
+typedef struct tfg_forcing_grid {
+  int32_t gny, gnx;   /* source nodes: rows, columns; each >= 1                     */
+  int32_t method;     /* TFG_REGRID_NEAREST / TFG_REGRID_BILINEAR                   */
+  int32_t pad;
+  double  y0, x0;     /* source-grid coordinate (node j sits at coordinate j) of    */
+                      /* the centre of the GLOBAL model cell (row 0, column 0)      */
+  double  sy, sx;     /* source nodes per model cell along rows / columns; any      */
+                      /* finite value (negative: the source axis runs the other way)*/
+  int64_t row0;       /* this shard's first row in the global grid (>= 0)           */
+} tfg_forcing_grid;
+int tfg_set_gridded_forcing(tfg_handle* h, int frame0, int nframes, const double* src, int src_on_device,
+                            const double* z_src, const tfg_forcing_grid* g, const tfg_downscale* ds);
+
 /* The eight BMI outputs in _output_vars order (:28-37): h_snow, h_swe, SM,
  * h_ice, h_iwe, IM, M_total, RH, as dst[8][n], from output-history slot
  * `hist` (h_swe/h_iwe: the current state).  One gather and one copy.

@@ -497,7 +497,7 @@ __global__ void k_terrain(const R* __restrict__ elev, const double* __restrict__
 #include "tfg_flow.hpp"  // the optional ice-flow kernels (tfg_ice_flow_*)
 #include "tfg_series.hpp"  // per-catchment sums of history planes (tfg_catchment_series)
 #include "tfg_aggregate.hpp"  // per-cell time aggregates of history planes (tfg_cell_aggregate)
-#include "tfg_forcing.hpp"  // per-catchment forcing spread over the grid (tfg_set_catchment_forcing)
+#include "tfg_forcing.hpp"  // forcing spread over the grid: per catchment (tfg_set_catchment_forcing), regridded (tfg_set_gridded_forcing)
 
 // tfg_set_inputs / tfg_get_outputs: the per-step BMI traffic of one call each.
 // src [5][n]: P_air, Hum_sp, P, T_air, uz (BMI order) -> frame planes.
@@ -576,6 +576,10 @@ enum : uint8_t { kUnknown = 0, kOk = 1, kDirty = 2 };
 
 // BMI input order (P_air, Hum_sp, P, T_air, uz) -> plane of a device forcing frame, on the host
 constexpr int kBmiToPlane[5] = {F_PA, F_Q, F_P, F_T, F_UZ};
+static_assert(kBmiToPlane[0] == tfg::kInputPlane[0] && kBmiToPlane[1] == tfg::kInputPlane[1] &&
+                  kBmiToPlane[2] == tfg::kInputPlane[2] && kBmiToPlane[3] == tfg::kInputPlane[3] &&
+                  kBmiToPlane[4] == tfg::kInputPlane[4],
+              "k_forcing_regrid's plane of a source field is tfg_set_inputs' plane");
 
 // tfg_selftest_powers: the fp64 engine's power rewrites (tfg_physics.hpp) and
 // its exp / log / constant-divisor division (tfg_fastmath.hpp) on device, with
@@ -652,8 +656,8 @@ struct Stream : Owned<hipStream_t, hipStreamDestroy> {
 
 // Two pinned slots for host data that is borrowed for one call only: the call
 // copies it into the slot whose previous transfer has completed and queues the
-// transfer from there (tfg_set_inputs and tfg_set_catchment_forcing share one
-// ring, each slot with a device buffer of its own; tfg_step stages its
+// transfer from there (tfg_set_inputs, tfg_set_catchment_forcing and
+// tfg_set_gridded_forcing share one ring, each slot with a device buffer of its own; tfg_step stages its
 // uniforms through another, into d_u / d_u2).
 struct StageRing {
   struct Slot {
@@ -752,7 +756,7 @@ struct tfg_handle {
   Dev<double> cond_halo;         // [2 sides][4][nx] f64 halo rows (T_snow, h_snow, T_ice, h_ice)
   Dev<double> cond_edges;        // [2 rows][4][nx] f64 this shard's edge rows
   double inv_cs = 0.0, inv_ci = 0.0, h_active = 0.0;  // 1/(rho_s Cp_s), 1/(rho_i Cp_i h_al), h_al
-  // tfg_set_inputs and tfg_set_catchment_forcing: host sources go through this ring
+  // tfg_set_inputs, tfg_set_catchment_forcing and tfg_set_gridded_forcing: host sources go through this ring
   StageRing in_ring;
   // tfg_get_outputs: device gather buffer + pinned host buffer
   Dev<void> out_d;
@@ -1199,7 +1203,7 @@ int tfg_abi_version(void) { return TFG_ABI_VERSION; }
 #if !defined(__HIP_DEVICE_COMPILE__)
 __attribute__((used)) static const char tfg_build_tag[] =
     "libtfg abi=" TFG_STR(TFG_ABI_VERSION) " arch=gfx950 (hipcc) tfg-src-sha256=" TFG_SRC_HASH
-    "; kernels: k_fused<float|double,exact|fast,...>, k_cell, k_cell_run, k_cell_many, k_diag_reduce, k_catch_series, k_forcing_expand, k_fill_synthetic";
+    "; kernels: k_fused<float|double,exact|fast,...>, k_cell, k_cell_run, k_cell_many, k_diag_reduce, k_catch_series, k_forcing_expand, k_forcing_regrid, k_fill_synthetic";
 
 const char* tfg_build_info(void) { return tfg_build_tag; }
 #else
@@ -2031,6 +2035,35 @@ int tfg_set_inputs(tfg_handle* h, int frame, const void* src, int src_dtype, int
   return TFG_OK;
 }
 
+namespace {
+// The checks of a tfg_downscale (NULL: every term off); *on: whether a term is on.
+int check_downscale(tfg_handle* h, const tfg_downscale* ds, const char* what, bool* on) {
+  *on = false;
+  if (!ds) return TFG_OK;
+  const std::string w = std::string(what) + ": ";
+  if (!std::isfinite(ds->lapse_T) || !std::isfinite(ds->grad_P)) return fail(h, TFG_ERR_ARG, w + "lapse_T and grad_P must be finite");
+  if (!std::isfinite(ds->rh_max) || ds->rh_max < 0.0) return fail(h, TFG_ERR_ARG, w + "rh_max must be finite and >= 0");
+  if (ds->pressure != 0 && ds->pressure != 1) return fail(h, TFG_ERR_ARG, w + "pressure must be 0 or 1");
+  *on = ds->lapse_T != 0.0 || ds->grad_P != 0.0 || ds->rh_max > 0.0 || ds->pressure == 1;
+  return TFG_OK;
+}
+// The forcing kernels' terms (ds == NULL: all off) with the handle's model constants.
+ForcingDs forcing_ds(const tfg_handle* h, const tfg_downscale* ds) {
+  ForcingDs d{};
+  if (ds) {
+    d.lapse_T = ds->lapse_T;
+    d.grad_P = ds->grad_P;
+    d.rh_max = ds->rh_max;
+    d.pressure = ds->pressure;
+  }
+  d.negM_g_R = h->dp.negM_g_R;
+  d.eps = h->dp.eps;
+  d.one_minus_eps = h->dp.one_minus_eps;
+  d.satterlund = h->dp.satterlund;
+  return d;
+}
+}  // namespace
+
 int tfg_set_catchment_forcing(tfg_handle* h, int frame0, int nframes, const double* table, int table_on_device,
                               const double* z_ref, const tfg_downscale* ds) {
   if (int rc_ = api_sync(h)) return rc_;  // after a split launch's second part
@@ -2039,14 +2072,7 @@ int tfg_set_catchment_forcing(tfg_handle* h, int frame0, int nframes, const doub
   if (frame0 < 0 || nframes < 1 || (int64_t)frame0 + nframes > h->n_frames)
     return fail(h, TFG_ERR_ARG, "catchment forcing: frames outside 0..n_frames");
   bool on = false;
-  if (ds) {
-    if (!std::isfinite(ds->lapse_T) || !std::isfinite(ds->grad_P))
-      return fail(h, TFG_ERR_ARG, "catchment forcing: lapse_T and grad_P must be finite");
-    if (!std::isfinite(ds->rh_max) || ds->rh_max < 0.0)
-      return fail(h, TFG_ERR_ARG, "catchment forcing: rh_max must be finite and >= 0");
-    if (ds->pressure != 0 && ds->pressure != 1) return fail(h, TFG_ERR_ARG, "catchment forcing: pressure must be 0 or 1");
-    on = ds->lapse_T != 0.0 || ds->grad_P != 0.0 || ds->rh_max > 0.0 || ds->pressure == 1;
-  }
+  if (int rc = check_downscale(h, ds, "catchment forcing", &on)) return rc;
   if (on && !z_ref) return fail(h, TFG_ERR_ARG, "catchment forcing: a downscaling term needs z_ref");
   HIPCHK(h, hipSetDevice(h->device));
   const size_t frame_len = (size_t)5 * h->n_catch;  // table entries per frame
@@ -2073,17 +2099,7 @@ int tfg_set_catchment_forcing(tfg_handle* h, int frame0, int nframes, const doub
         h->plane_state[(size_t)(frame0 + j) * kNumForc + kBmiToPlane[f]] =
             (table_on_device || on) ? kUnknown : host_finite_as_f32(table + (size_t)j * frame_len + (size_t)f * h->n_catch, h->n_catch);
   }
-  ForcingDs d{};
-  if (on) {
-    d.lapse_T = ds->lapse_T;
-    d.grad_P = ds->grad_P;
-    d.rh_max = ds->rh_max;
-    d.pressure = ds->pressure;
-  }
-  d.negM_g_R = h->dp.negM_g_R;
-  d.eps = h->dp.eps;
-  d.one_minus_eps = h->dp.one_minus_eps;
-  d.satterlund = h->dp.satterlund;
+  const ForcingDs d = forcing_ds(h, on ? ds : nullptr);
   const bool wide = forcing_wide();
   for (int j0 = 0; j0 < nframes; j0 += kForcingBatch) {
     const int nb = std::min(kForcingBatch, nframes - j0);
@@ -2098,6 +2114,73 @@ int tfg_set_catchment_forcing(tfg_handle* h, int frame0, int nframes, const doub
       };
       if (wide) { if (on) launch(k_forcing_expand<R, true, V>, V); else launch(k_forcing_expand<R, false, V>, V); }
       else { if (on) launch(k_forcing_expand<R, true, 1>, 1); else launch(k_forcing_expand<R, false, 1>, 1); }
+    });
+    HIPCHK(h, hipGetLastError());
+  }
+  if (s) HIPCHK(h, StageRing::commit(*s, h->stream));
+  return TFG_OK;
+}
+
+int tfg_set_gridded_forcing(tfg_handle* h, int frame0, int nframes, const double* src, int src_on_device,
+                            const double* z_src, const tfg_forcing_grid* g, const tfg_downscale* ds) {
+  if (int rc_ = api_sync(h)) return rc_;  // after a split launch's second part
+  if (!h) return fail(nullptr, TFG_ERR_ARG, "null handle");
+  if (!src) return fail(h, TFG_ERR_ARG, "gridded forcing: null src");
+  if (!g) return fail(h, TFG_ERR_ARG, "gridded forcing: null grid");
+  if (frame0 < 0 || nframes < 1 || (int64_t)frame0 + nframes > h->n_frames)
+    return fail(h, TFG_ERR_ARG, "gridded forcing: frames outside 0..n_frames");
+  if (g->gny < 1 || g->gnx < 1) return fail(h, TFG_ERR_ARG, "gridded forcing: gny and gnx must be >= 1");
+  if ((int64_t)g->gny * g->gnx >= ((int64_t)1 << 29))  // k_forcing_regrid's 32-bit byte offsets into a field
+    return fail(h, TFG_ERR_ARG, "gridded forcing: a source field must be under 4 GiB (gny * gnx < 2^29)");
+  if (g->method != TFG_REGRID_NEAREST && g->method != TFG_REGRID_BILINEAR)
+    return fail(h, TFG_ERR_ARG, "gridded forcing: method must be TFG_REGRID_NEAREST or TFG_REGRID_BILINEAR");
+  if (!std::isfinite(g->y0) || !std::isfinite(g->x0) || !std::isfinite(g->sy) || !std::isfinite(g->sx))
+    return fail(h, TFG_ERR_ARG, "gridded forcing: y0, x0, sy and sx must be finite");
+  if (g->row0 < 0) return fail(h, TFG_ERR_ARG, "gridded forcing: row0 must be >= 0");
+  bool on = false;
+  if (int rc = check_downscale(h, ds, "gridded forcing", &on)) return rc;
+  if (on && !z_src) return fail(h, TFG_ERR_ARG, "gridded forcing: a downscaling term needs z_src");
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t gnode = (size_t)g->gny * (size_t)g->gnx, frame_len = 5 * gnode;  // source nodes, values per frame
+  const double* dsrc = src;
+  const double* dz = on ? z_src : nullptr;
+  StageRing::Slot* s = nullptr;
+  if (!src_on_device) {
+    // borrowed for this call only: src | z_src through the staging ring, one queued copy
+    const size_t sbytes = (size_t)nframes * frame_len * 8, bytes = sbytes + (on ? gnode * 8 : 0);
+    HIPCHK(h, h->in_ring.acquire(bytes, true, &s));
+    std::memcpy(s->host.ptr, src, sbytes);
+    if (on) std::memcpy(static_cast<char*>(s->host.ptr) + sbytes, z_src, gnode * 8);
+    HIPCHK(h, hipMemcpyAsync(s->dev.ptr, s->host.ptr, bytes, hipMemcpyHostToDevice, h->stream));
+    dsrc = static_cast<const double*>(s->dev.ptr);
+    if (on) dz = dsrc + (size_t)nframes * frame_len;
+  }
+  if (h->engine == TFG_F32) {
+    // finite-data tracking: a plain plane holds values between its field's
+    // nodes, so a host field that is finite as fp32 leaves a finite plane; a
+    // field with a NaN node may or may not reach a cell, and a device source or
+    // a downscaled plane is not looked at: those are checked lazily
+    for (int j = 0; j < nframes; ++j)
+      for (int f = 0; f < 5; ++f) {  // the source's fields are in BMI order
+        const bool finite = !src_on_device && !on && host_finite_as_f32(src + (size_t)j * frame_len + (size_t)f * gnode, (int64_t)gnode) == kOk;
+        h->plane_state[(size_t)(frame0 + j) * kNumForc + kBmiToPlane[f]] = finite ? kOk : kUnknown;
+      }
+  }
+  const ForcingDs d = forcing_ds(h, on ? ds : nullptr);
+  const bool bilinear = g->method == TFG_REGRID_BILINEAR;
+  for (int j0 = 0; j0 < nframes; j0 += kForcingBatch) {
+    const int nb = std::min(kForcingBatch, nframes - j0);
+    char* fr = h->forc.bytes() + (size_t)(frame0 + j0) * kNumForc * h->n_pad * h->rsz;
+    const double* sb = dsrc + (size_t)j0 * frame_len;
+    by_type(h->engine, [&](auto t) {
+      using R = typename decltype(t)::type;
+      constexpr int V = 16 / (int)sizeof(R);  // cells per lane: 16-byte stores
+      auto launch = [&](auto kern) {
+        hipLaunchKernelGGL(kern, forcing_blocks(h->n, V), kBlock, 0, h->stream, (R*)fr, h->n_pad, nb, sb, dz,
+                           (const R*)h->stat.ptr, h->n, h->nx, *g, d);
+      };
+      if (on) { if (bilinear) launch(k_forcing_regrid<R, true, true, V>); else launch(k_forcing_regrid<R, true, false, V>); }
+      else { if (bilinear) launch(k_forcing_regrid<R, false, true, V>); else launch(k_forcing_regrid<R, false, false, V>); }
     });
     HIPCHK(h, hipGetLastError());
   }

@@ -60,6 +60,16 @@ class TfgDownscale(ctypes.Structure):
                 ("pressure", ctypes.c_int32), ("pad", ctypes.c_int32)]
 
 
+REGRID_NEAREST, REGRID_BILINEAR = 0, 1  # include/tfg.h TFG_REGRID_*
+
+
+class TfgForcingGrid(ctypes.Structure):
+    """tfg_forcing_grid: the source grid and its map to the model grid (tfg_set_gridded_forcing)."""
+    _fields_ = [("gny", ctypes.c_int32), ("gnx", ctypes.c_int32), ("method", ctypes.c_int32), ("pad", ctypes.c_int32),
+                ("y0", ctypes.c_double), ("x0", ctypes.c_double), ("sy", ctypes.c_double), ("sx", ctypes.c_double),
+                ("row0", ctypes.c_int64)]
+
+
 class TfgCellStats(ctypes.Structure):
     """tfg_cell_stats: the accumulators of tfg_cell_aggregate (device pointers, or None)."""
     _fields_ = [("sum", ctypes.c_void_p), ("vmax", ctypes.c_void_p), ("vmin", ctypes.c_void_p),
@@ -131,6 +141,8 @@ def load() -> ctypes.CDLL:
         "tfg_ice_flow_run": ([vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, i32], i32),
         "tfg_set_inputs": ([vp, i32, vp, i32, i64, i32], i32),
         "tfg_set_catchment_forcing": ([vp, i32, i32, vp, i32, vp, ctypes.POINTER(TfgDownscale)], i32),
+        "tfg_set_gridded_forcing": ([vp, i32, i32, vp, i32, vp, ctypes.POINTER(TfgForcingGrid),
+                                     ctypes.POINTER(TfgDownscale)], i32),
         "tfg_get_outputs": ([vp, i32, vp, i32, i64, i32], i32),
         "tfg_update": ([vp, i32, vp, i32, vp, vp, i32, i64], i32),
         "tfg_update_many": ([vp, i32, vp, vp, vp], i32),
@@ -315,4 +327,5 @@ def exported_symbols() -> list[str]:
         "tfg_update", "tfg_update_many", "tfg_conduction_edges", "tfg_conduction_update", "tfg_conduction_off",
         "tfg_nan_safe_launches", "tfg_set_step_form", "tfg_set_flux", "tfg_set_split", "tfg_join", "tfg_get_split",
         "tfg_selftest_powers", "tfg_catchment_series", "tfg_set_catchment_forcing", "tfg_cell_aggregate",
+        "tfg_set_gridded_forcing",
     ) if hasattr(L, n)]

@@ -282,6 +282,69 @@ class GlacierEngine:
         self._chk(self.lib.tfg_set_catchment_forcing(self.h, int(frame0), int(a.shape[0]),
                                                      a.ctypes.data_as(ctypes.c_void_p), 0, zp, dsp))
 
+    def set_gridded_forcing(self, src, grid, frame0: int = 0, z_src=None, downscale=None) -> None:
+        """Forcing frames frame0 .. frame0+nframes-1 from fields on a regular
+        source grid, src [nframes][5][gny][gnx] (tfg_set_inputs order P_air,
+        Hum_sp, P, T_air, uz), interpolated onto the model grid on the device
+        (tfg_set_gridded_forcing).  `grid` is a forcing.ForcingGrid: the source
+        grid's size, its affine map to the global model grid and the method
+        ("bilinear" or "nearest"); the engine adds its own row0, so row-block
+        shards pass the same grid and source.  With a term of `downscale` (a
+        forcing.Downscale) on, the interpolated values are corrected for the
+        cell's height above z_src [gny][gnx], the source grid's elevation
+        interpolated by the same method.
+
+        `src` (and z_src) is a host array, or a contiguous float64 torch CUDA
+        tensor on the engine's device, read asynchronously on the engine's
+        stream under set_catchment_forcing's stream rules."""
+        if grid.method not in grid.METHODS:
+            raise ValueError(f"method must be one of {grid.METHODS}, not {grid.method!r}")
+        gny, gnx = int(grid.gny), int(grid.gnx)
+        g = nat.TfgForcingGrid(gny, gnx, grid.METHODS.index(grid.method), 0, float(grid.y0), float(grid.x0),
+                               float(grid.sy), float(grid.sx), self.row0)
+        ds = None
+        if downscale is not None:
+            ds = nat.TfgDownscale(float(downscale.lapse_T), float(downscale.grad_P), float(downscale.rh_max),
+                                  int(downscale.pressure), 0)
+        dsp = ctypes.byref(ds) if ds is not None else None
+        if getattr(src, "is_cuda", False):
+            import torch
+
+            tensors = [src] + ([z_src] if z_src is not None else [])
+            if src.dim() != 4 or tuple(src.shape[1:]) != (5, gny, gnx):
+                raise ValueError(f"src must be [nframes][5][{gny}][{gnx}]")
+            if z_src is not None and not (getattr(z_src, "is_cuda", False) and tuple(z_src.shape) == (gny, gnx)):
+                raise ValueError(f"z_src must be a CUDA tensor [{gny}][{gnx}], like src")
+            for t in tensors:
+                if t.device.index != self.device:
+                    raise ValueError(f"src on {t.device}, the engine runs on cuda:{self.device}")
+                if t.dtype != torch.float64 or not t.is_contiguous():
+                    raise ValueError("src and z_src must be contiguous float64 tensors")
+            own = getattr(self, "_stream_ptr", None)
+            cur = torch.cuda.current_stream(src.device)
+            if own is None or own != cur.cuda_stream:
+                cur.synchronize()
+            zp = ctypes.c_void_p(z_src.data_ptr()) if z_src is not None else None
+            self._chk(self.lib.tfg_set_gridded_forcing(self.h, int(frame0), int(src.shape[0]),
+                                                       ctypes.c_void_p(src.data_ptr()), 1, zp, ctypes.byref(g), dsp))
+            ptr = own or self.stream()
+            if getattr(self, "_ext_stream", (None, None))[0] != ptr:
+                self._ext_stream = (ptr, torch.cuda.ExternalStream(ptr, device=src.device))
+            for t in tensors:
+                t.record_stream(self._ext_stream[1])
+            return
+        a = np.ascontiguousarray(src, dtype=np.float64)
+        if a.ndim != 4 or a.shape[1:] != (5, gny, gnx):
+            raise ValueError(f"src must be [nframes][5][{gny}][{gnx}]")
+        zp = None
+        if z_src is not None:
+            z = np.ascontiguousarray(z_src, dtype=np.float64)
+            if z.shape != (gny, gnx):
+                raise ValueError(f"z_src must be [{gny}][{gnx}]")
+            zp = z.ctypes.data_as(ctypes.c_void_p)
+        self._chk(self.lib.tfg_set_gridded_forcing(self.h, int(frame0), int(a.shape[0]),
+                                                   a.ctypes.data_as(ctypes.c_void_p), 0, zp, ctypes.byref(g), dsp))
+
     def catchment_mean_elevation(self):
         """(sum [n_catch], cells [n_catch]) of this shard: per catchment, the
         sum of the elevation raster as the engine holds it (fp32-rounded in

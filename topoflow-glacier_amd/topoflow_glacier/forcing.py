@@ -28,7 +28,7 @@ from pathlib import Path
 import numpy as np
 
 __all__ = ["BMI_INPUTS", "INTERNAL", "K_TO_C", "ForcingTable", "read_forcing_csv", "frames_from_table",
-           "INPUT_ORDER", "Downscale", "catchment_table"]
+           "INPUT_ORDER", "Downscale", "catchment_table", "ForcingGrid"]
 
 K_TO_C = -273.15  # BmiTopoflowGlacier.K_to_C (bmi_topoflow_glacier.py:290)
 
@@ -143,3 +143,51 @@ def catchment_table(tables) -> np.ndarray:
         for v, name in enumerate(INPUT_ORDER):
             out[:, v, c] = t.inputs[name]
     return out
+
+
+def _axis_map(src, first: float, step: float, name: str):
+    """(origin, scale) of one axis: the source-grid coordinate (node j at j) of
+    model cell k is origin + scale k, from the nodes' coordinates `src` and
+    the cell centres first + step k."""
+    src = np.asarray(src, dtype=np.float64).reshape(-1)
+    if src.size < 1 or not np.isfinite(src).all():
+        raise ValueError(f"ForcingGrid.from_axes: {name} needs at least one finite node coordinate")
+    if src.size == 1:  # one node: every coordinate clamps to it
+        return 0.0, 0.0
+    h = (src[-1] - src[0]) / (src.size - 1)
+    if h == 0.0 or np.abs(np.diff(src) - h).max() > 1e-6 * abs(h):
+        raise ValueError(f"ForcingGrid.from_axes: {name} is not uniformly spaced")
+    return float((first - src[0]) / h), float(step / h)
+
+
+@dataclass
+class ForcingGrid:
+    """A regular source grid under GlacierEngine.set_gridded_forcing
+    (tfg_forcing_grid): gny x gnx nodes, node (j, i) at source-grid coordinate
+    (j, i).  The centre of the GLOBAL model cell (row R, column c) sits at the
+    source-grid coordinate (y0 + sy R, x0 + sx c); a negative sy or sx is a
+    source axis that runs against the model's.  Outside the source grid the
+    edge value is held.  method: "bilinear" or "nearest" (ties go up)."""
+
+    gny: int
+    gnx: int
+    y0: float = 0.0
+    x0: float = 0.0
+    sy: float = 1.0
+    sx: float = 1.0
+    method: str = "bilinear"
+
+    METHODS = ("nearest", "bilinear")  # include/tfg.h TFG_REGRID_*
+
+    @classmethod
+    def from_axes(cls, src_y, src_x, y_first: float, x_first: float, dy: float, dx: float,
+                  method: str = "bilinear") -> "ForcingGrid":
+        """The affine map from the source nodes' coordinates src_y [gny] and
+        src_x [gnx] (uniformly spaced, ascending or descending, in the model
+        grid's coordinate system) and the model grid: the centre of its cell
+        (row 0, column 0) at (y_first, x_first), rows dy and columns dx apart
+        (signed: dy < 0 for rows that run north to south).  Raises ValueError
+        on an axis that is not uniformly spaced."""
+        y0, sy = _axis_map(src_y, float(y_first), float(dy), "src_y")
+        x0, sx = _axis_map(src_x, float(x_first), float(dx), "src_x")
+        return cls(gny=int(np.size(src_y)), gnx=int(np.size(src_x)), y0=y0, x0=x0, sy=sy, sx=sx, method=method)

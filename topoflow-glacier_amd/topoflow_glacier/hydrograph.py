@@ -96,12 +96,49 @@ def forced_catchment_hydrographs(eng, table, z_ref=None, downscale=None, group=N
 
             z_ref = torch.from_numpy(z_ref).to(table.device)
 
+    def write(k0, k1, frame0):
+        eng.set_catchment_forcing(table[k0:k1], frame0=frame0, z_ref=z_ref, downscale=downscale)
+
+    return _frame_ring_hydrographs(eng, nsteps, write, group, taps)
+
+
+def _frame_ring_hydrographs(eng, nsteps: int, write, group, taps: int) -> dict:
+    """catchment_hydrographs with step k reading frame k % n_frames:
+    write(k0, k1, frame0) produces the frames of steps k0..k1-1 from frame0 on,
+    before the block that reads them is queued; a block that wraps the frame
+    ring takes two calls."""
+    nf = int(eng.n_frames)
+
     def write_frames(k0, k1):
         f0 = k0 % nf
         head = min(k1 - k0, nf - f0)
-        eng.set_catchment_forcing(table[k0:k0 + head], frame0=f0, z_ref=z_ref, downscale=downscale)
+        write(k0, k0 + head, f0)
         if k0 + head < k1:  # the block wraps the frame ring
-            eng.set_catchment_forcing(table[k0 + head:k1], frame0=0, z_ref=z_ref, downscale=downscale)
+            write(k0 + head, k1, 0)
 
     frames = (np.arange(nsteps) % nf).astype(np.int32)
     return catchment_hydrographs(eng, nsteps, frames=frames, group=group, taps=taps, on_block=write_frames)
+
+
+def gridded_forced_hydrographs(eng, src, grid, z_src=None, downscale=None, group=None, taps: int = 20) -> dict:
+    """catchment_hydrographs driven by forcing on a regular source grid, src
+    [nsteps][5][gny][gnx] (a host array or a float64 CUDA tensor) with its
+    forcing.ForcingGrid: before each block of steps is queued, the block's
+    frames are interpolated onto the model grid on the device
+    (GlacierEngine.set_gridded_forcing), step k of this call into frame
+    k % n_frames, under forced_catchment_hydrographs' frame-ring rules
+    (n_frames >= hist_depth).  The forcing needs no collective: every rank of
+    `group` holds the same source grid and z_src [gny][gnx], and its engine
+    its own row0.
+
+    downscale  a forcing.Downscale; None or all-off leaves the interpolated values
+    z_src      the source grid's elevation, needed when a term is on
+    """
+    nsteps = int(src.shape[0])
+    if int(eng.n_frames) < int(eng.hist_depth):
+        raise ValueError(f"n_frames ({eng.n_frames}) must be >= hist_depth ({eng.hist_depth}): a block's frames are resident together")
+
+    def write(k0, k1, frame0):
+        eng.set_gridded_forcing(src[k0:k1], grid, frame0=frame0, z_src=z_src, downscale=downscale)
+
+    return _frame_ring_hydrographs(eng, nsteps, write, group, taps)
