@@ -245,6 +245,22 @@ __global__ __launch_bounds__(kBlock, EXACT ? kMinWavesExact : (PREC ? kMinWavesP
 
   CellDiag acc;
   diag_zero(acc);
+  // The fp32 engine's launch-long sums without catchments live in LDS, one
+  // slot per lane and field, not in registers: the step loop never touches
+  // them, and their 12 VGPRs are what it lacks to hold three frames without
+  // spilling.  Each lane adds to its own slots once per trip, in the order it
+  // added to the registers.
+  constexpr bool kAccLds = !EXACT && !CATCH;
+  __shared__ double acc_lds[kAccLds ? 6 * kBlock : 1];
+  auto acc_get = [&]() {
+    const double* s = acc_lds + threadIdx.x;
+    return CellDiag{s[0], s[kBlock], s[2 * kBlock], s[3 * kBlock], s[4 * kBlock], s[5 * kBlock]};
+  };
+  auto acc_put = [&](const CellDiag& d) {
+    double* s = acc_lds + threadIdx.x;
+    s[0] = d.P; s[kBlock] = d.PR; s[2 * kBlock] = d.PS; s[3 * kBlock] = d.SM; s[4 * kBlock] = d.IM; s[5 * kBlock] = d.Pmax;
+  };
+  if constexpr (kAccLds) acc_put(acc);
 
   for (int64_t it = 0; it < trips; ++it) {
     const int64_t g = g0 + it * kBlock + threadIdx.x;
@@ -258,7 +274,6 @@ __global__ __launch_bounds__(kBlock, EXACT ? kMinWavesExact : (PREC ? kMinWavesP
     if (in) {
       const int64_t c0 = g * C;
       const uint32_t lc = (uint32_t)c0;  // element index within every field
-      if constexpr (CATCH) iload<C>(catch_id, lc, cid);
       // static geometry: the planes k_prepare_static (exact engine, fp64 in
       // reference op order) or k_prepare_geo (fast engine) wrote
       CellStatic SX[EXACT ? C : 1];
@@ -411,6 +426,12 @@ __global__ __launch_bounds__(kBlock, EXACT ? kMinWavesExact : (PREC ? kMinWavesP
                                                    o, df[j], (float)qc[j]);
             o_hs[j] = (R)o.h_snow; o_sm[j] = (R)o.SM; o_hi[j] = (R)o.h_ice;
             o_im[j] = (R)o.IM; o_mt[j] = (R)o.M_total; o_rh[j] = (R)o.RH;
+            // The running maximum of P is taken in this step, not batched
+            // with later steps' at the end of an unrolled round: a batch keeps
+            // this frame's P live past the next request into its registers,
+            // which then lands elsewhere and is copied at the back edge,
+            // behind a wait for a frame requested only a step earlier.
+            asm volatile("" : "+v"(df[j].P), "+v"(df[j].PR), "+v"(df[j].PS), "+v"(df[j].Pmax));
           }
         }
         const uint32_t oR = lane_off(lc * (uint32_t)sizeof(R));
@@ -433,11 +454,26 @@ __global__ __launch_bounds__(kBlock, EXACT ? kMinWavesExact : (PREC ? kMinWavesP
       // one step per launch).  The conduction (QC) and NaN-safe (NS) forms keep
       // one step ahead: with two they spill 2-4 VGPRs.
       constexpr int kAhead = (QC || NS || PREC) ? 1 : kPrefetchFast;
+      //
+      // Loads and stores share one in-order counter per wave (vmcnt), and the
+      // compiler sizes each wait for the shortest queue of accesses that can
+      // stand behind the frame on any path to it.  So every edge into a loop's
+      // header has to carry the same queue: the first round of the fp32 loops is
+      // peeled (the trip's prologue has no stores in flight, the back edge has
+      // a step's seven), the loop body has no conditional step (a step that
+      // may not have run leaves its stores "maybe issued"), and the last one
+      // or two steps of a launch run in a tail of their own.  The waits of the
+      // loop are then exact: the 26 accesses (7 + 6 + 7 + 6) behind a frame two
+      // steps ahead, 13 behind one a step ahead (scripts/step_loop_waits.py,
+      // DESIGN.md section 5).  A one-step launch (K >= 1 always) leaves `fa`
+      // its step's frame: tfg_update below writes it to the frames.
       Frame fa, fb;
       fetch(0, fa);
       if constexpr (EXACT) {
         // the fp64 step is issue-bound and register-heavy: one copy of its
-        // body (not two interleaved) keeps it within 256 VGPRs
+        // body (not two interleaved) keeps it within 256 VGPRs.  Not peeled:
+        // `fa = fb` waits for the frame a step after its request either way
+        // (vmcnt 6 or 7), and peeled it measured 1.2 % slower at 4096^2.
         for (int k = 0; k < a.K; ++k) {
           fetch(k + 1, fb);
           advance(k, fa);
@@ -446,21 +482,52 @@ __global__ __launch_bounds__(kBlock, EXACT ? kMinWavesExact : (PREC ? kMinWavesP
       } else if constexpr (kAhead == 2) {
         Frame fc;
         fetch(1, fb);
-        for (int k = 0; k < a.K; k += 3) {
-          fetch(k + 2, fc);
-          advance(k, fa);
-          fetch(k + 3, fa);
-          if (k + 1 < a.K) advance(k + 1, fb);
-          fetch(k + 4, fb);
-          if (k + 2 < a.K) advance(k + 2, fc);
+        int k = 0;
+        if (a.K >= 3) {
+          fetch(2, fc);
+          advance(0, fa);
+          fetch(3, fa);
+          advance(1, fb);
+          fetch(4, fb);
+          advance(2, fc);
+          for (k = 3; k + 3 <= a.K; k += 3) {
+            fetch(k + 2, fc);
+            advance(k, fa);
+            fetch(k + 3, fa);
+            advance(k + 1, fb);
+            fetch(k + 4, fb);
+            advance(k + 2, fc);
+          }
         }
-      } else {
+        if (k < a.K) {  // fa and fb hold the frames of steps k and k + 1
+          advance(k, fa);
+          if (k + 1 < a.K) advance(k + 1, fb);
+        }
+      } else if constexpr (PREC && CATCH) {
+        // The fp64-flux form with catchments keeps the loop of conditional
+        // steps: it is 6-10 VGPRs over its 128 already, and peeled its spills
+        // move into the step loop.
         for (int k = 0; k < a.K; k += 2) {
           fetch(k + 1, fb);
           advance(k, fa);
           fetch(k + 2, fa);
           if (k + 1 < a.K) advance(k + 1, fb);
         }
+      } else {
+        int k = 0;
+        if (a.K >= 2) {
+          fetch(1, fb);
+          advance(0, fa);
+          fetch(2, fa);
+          advance(1, fb);
+          for (k = 2; k + 2 <= a.K; k += 2) {
+            fetch(k + 1, fb);
+            advance(k, fa);
+            fetch(k + 2, fa);
+            advance(k + 1, fb);
+          }
+        }
+        if (k < a.K) advance(k, fa);  // fa holds the frame of step k
       }
       if (a.io_in) {  // tfg_update: the frame keeps the inputs, outputs go to the host block
         const int fidx = uni[0].frame, hidx = uni[0].hist;
@@ -485,6 +552,9 @@ __global__ __launch_bounds__(kBlock, EXACT ? kMinWavesExact : (PREC ? kMinWavesP
           o[7 * n] = (double)hs[H_RH * n_pad];
         }
       }
+      // the catchment ids are read here, behind the step loop, where they are
+      // first needed: a register less across the loop
+      if constexpr (CATCH) iload<C>(catch_id, lc, cid);
       // fast engine: fold the cell's partial sums into the fp64 accumulators
       // with the constant factors of :567, :585-623, :1486, :1493 (padding
       // cells excluded)
@@ -494,13 +564,16 @@ __global__ __launch_bounds__(kBlock, EXACT ? kMinWavesExact : (PREC ? kMinWavesP
 #pragma unroll
         for (int j = 0; j < C; ++j) {
           if ((c0 + j) < a.n) {
-            CellDiag& d = CATCH ? cacc[j] : acc;
+            CellDiag lsum;
+            if constexpr (kAccLds) lsum = acc_get();
+            CellDiag& d = CATCH ? cacc[j] : (kAccLds ? lsum : acc);
             d.P += (double)df[j].P * fP;
             d.PR += (double)df[j].PR * fP;
             d.PS += (double)df[j].PS * fP;
             d.SM += (double)df[j].Erem_s * fSM;
             d.IM += (double)df[j].IM * fIM;
             d.Pmax = tfg::npmax(d.Pmax, (double)df[j].Pmax);
+            if constexpr (kAccLds) acc_put(lsum);
           }
         }
       }
@@ -547,6 +620,7 @@ __global__ __launch_bounds__(kBlock, EXACT ? kMinWavesExact : (PREC ? kMinWavesP
     }
   }
   if constexpr (EXACT && !CATCH) diag_scale(acc, p);
+  if constexpr (kAccLds) acc = acc_get();
   if constexpr (!CATCH) wave_flush(wbins, 0, acc, true);
   __syncthreads();
   // each workgroup accumulates into its own slab row across launches (fixed
