@@ -364,6 +364,52 @@ int tfg_reset_diag(tfg_handle* h);
  * cells -- with TFG_OUT_M_TOTAL, times da_m2, a hydrograph per catchment. */
 int tfg_catchment_series(tfg_handle* h, int field, int hist0, int nslots, double* out, int out_on_device);
 
+/* Per-catchment, per-elevation-band sums and counts of one output field over
+ * history slots, reduced on the device.  The band is a second key next to the
+ * catchment id, taken at call time from the elevation raster the handle holds
+ * against edges the caller chooses.  For every cell i < ny*nx:
+ *   c = catch_id[i], or 0 without a raster;
+ *   z = (double)elev[i] as the handle holds it (the fp32 engine: the
+ *       fp32-rounded value);
+ *   the cell is in band k iff edges[k] <= z < edges[k+1] -- numpy's
+ *   np.searchsorted(edges, z, side="right") - 1, kept when in 0 .. n_bands-1.
+ * A cell with z < edges[0], z >= edges[n_bands] or NaN z is in no band and
+ * contributes to nothing, whatever its values are.
+ *   sum  [nslots][n_catch][n_bands] fp64   the sum of field[slot (hist0 + j) %
+ *        hist_depth][i] over the cells of (c, k), accumulated in fp64, unscaled
+ *   count[nslots][n_catch][n_bands] int64  the number of those cells with
+ *        (double)value > threshold; a NaN value is never counted
+ *   cells        [n_catch][n_bands] int64  the number of cells of (c, k): the
+ *        hypsometry, independent of the field
+ * A NULL pointer leaves that output out; at least one is set.  With sum ==
+ * NULL && count == NULL no history plane is read (field, hist0 and nslots are
+ * still validated).  An empty (c, k) reads 0.  No floating-point atomics and
+ * no dependence on dispatch order: two calls give the same bits, and a (slot,
+ * catchment, band) entry is the same bit for bit whichever other slots share
+ * the call and wherever in a batch it sits.  A NaN value reaches exactly the
+ * sum entry of its own (slot, catchment, band).
+ * out_on_device == 0: the outputs are host memory and the call blocks.
+ * Otherwise they are device pointers and the call is queued on the handle's
+ * stream (after the second part of a split launch), without a host wait.
+ * `edges` is always host memory and is consumed before the call returns.
+ * TFG_ERR_ARG, with nothing written: a null handle, b or edges; all three
+ * outputs NULL; n_bands outside 1..64; n_catch * n_bands > 2048; an edge that
+ * is not finite or not above the one before; a NaN threshold with count set;
+ * a field that is not one of the six history fields; hist0 or nslots out of
+ * range (tfg_catchment_series's rule).
+ * Replaces: the per-step get_value loop of a caller of the reference that bins
+ * outputs by elevation (melt and runoff per band, snow-covered fraction per
+ * band, the snow line); the reference has one cell per catchment and no
+ * counterpart of its own. */
+typedef struct tfg_bands {
+  int32_t n_bands;       /* 1 .. 64                                              */
+  int32_t pad;
+  const double* edges;   /* HOST, [n_bands + 1], finite, strictly ascending [m]  */
+  double threshold;      /* for `count`                                          */
+} tfg_bands;
+int tfg_band_series(tfg_handle* h, int field, int hist0, int nslots, const tfg_bands* b,
+                    double* sum, int64_t* count, int64_t* cells, int out_on_device);
+
 /* Per-cell time aggregates of one output field over history slots, folded on
  * the device.  For every cell i < ny*nx, with v_j = field[slot (hist0 + j) %
  * hist_depth][i] in the engine's element type, j = 0 .. nslots-1 in that

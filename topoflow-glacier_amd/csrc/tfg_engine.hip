@@ -496,6 +496,7 @@ __global__ void k_terrain(const R* __restrict__ elev, const double* __restrict__
 
 #include "tfg_flow.hpp"  // the optional ice-flow kernels (tfg_ice_flow_*)
 #include "tfg_series.hpp"  // per-catchment sums of history planes (tfg_catchment_series)
+#include "tfg_bands.hpp"  // per-catchment, per-elevation-band sums and counts of history planes (tfg_band_series)
 #include "tfg_aggregate.hpp"  // per-cell time aggregates of history planes (tfg_cell_aggregate)
 #include "tfg_forcing.hpp"  // forcing spread over the grid: per catchment (tfg_set_catchment_forcing), regridded (tfg_set_gridded_forcing)
 
@@ -730,6 +731,11 @@ struct tfg_handle {
   // tfg_catchment_series, allocated on first use: the workgroups' partial sums and a host call's result
   Dev<double> series_part;       // [series_blocks][kSeriesBatch][n_catch]
   Dev<double> series_out;        // [hist_depth][n_catch]
+  // tfg_band_series, allocated on first use: the workgroups' partials and a host call's results
+  Dev<double> band_part_sum;     // [band_blocks][band_batch][n_catch * n_bands]
+  Dev<int32_t> band_part_int;    // [band_blocks][band_batch * K + K]: counts, then cells
+  Dev<double> band_out_sum;      // [hist_depth][K]
+  Dev<int64_t> band_out_int;     // [hist_depth][K] counts, then [K] cells
   Dev<float> d_diurnal;
   Dev<int32_t> d_flag;
   // tfg_step's staged steps: [nsteps] tfg_uniforms, then the [nsteps] StepAddr
@@ -1203,7 +1209,7 @@ int tfg_abi_version(void) { return TFG_ABI_VERSION; }
 #if !defined(__HIP_DEVICE_COMPILE__)
 __attribute__((used)) static const char tfg_build_tag[] =
     "libtfg abi=" TFG_STR(TFG_ABI_VERSION) " arch=gfx950 (hipcc) tfg-src-sha256=" TFG_SRC_HASH
-    "; kernels: k_fused<float|double,exact|fast,...>, k_cell, k_cell_run, k_cell_many, k_diag_reduce, k_catch_series, k_forcing_expand, k_forcing_regrid, k_fill_synthetic";
+    "; kernels: k_fused<float|double,exact|fast,...>, k_cell, k_cell_run, k_cell_many, k_diag_reduce, k_catch_series, k_band_series, k_forcing_expand, k_forcing_regrid, k_fill_synthetic";
 
 const char* tfg_build_info(void) { return tfg_build_tag; }
 #else
@@ -1891,6 +1897,97 @@ int tfg_catchment_series(tfg_handle* h, int field, int hist0, int nslots, double
   }
   if (!out_on_device) {
     HIPCHK(h, hipMemcpyAsync(out, dout, (size_t)nslots * h->n_catch * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+  }
+  return TFG_OK;
+}
+
+int tfg_band_series(tfg_handle* h, int field, int hist0, int nslots, const tfg_bands* b, double* sum, int64_t* count,
+                    int64_t* cells, int out_on_device) {
+  if (int rc_ = api_sync(h)) return rc_;  // after a split launch's second part
+  if (!h) return fail(nullptr, TFG_ERR_ARG, "null handle");
+  if (!b || !b->edges) return fail(h, TFG_ERR_ARG, "band series: null bands or edges");
+  if (!sum && !count && !cells) return fail(h, TFG_ERR_ARG, "band series: no output requested");
+  if (b->n_bands < 1 || b->n_bands > kBandMaxBands) return fail(h, TFG_ERR_ARG, "band series: n_bands outside 1..64");
+  if ((int64_t)h->n_catch * b->n_bands > kBandMaxKeys)
+    return fail(h, TFG_ERR_ARG, "band series: n_catch * n_bands = " + std::to_string((int64_t)h->n_catch * b->n_bands) + " > 2048");
+  BandEdges edges{};
+  for (int k = 0; k <= b->n_bands; ++k) {
+    edges.e[k] = b->edges[k];
+    if (!std::isfinite(edges.e[k])) return fail(h, TFG_ERR_ARG, "band series: edge " + std::to_string(k) + " is not finite");
+    if (k && !(edges.e[k] > edges.e[k - 1])) return fail(h, TFG_ERR_ARG, "band series: edges must be strictly ascending");
+  }
+  if (count && b->threshold != b->threshold) return fail(h, TFG_ERR_ARG, "band series: NaN threshold");
+  if (!is_hist_field(field))
+    return fail(h, TFG_ERR_ARG, "band series: field " + std::to_string(field) +
+                                    " is not a history field (h_snow, SM, h_ice, IM, M_total, RH)");
+  if (hist0 < 0 || hist0 >= h->hist_depth) return fail(h, TFG_ERR_ARG, "band series: first history slot out of range");
+  if (nslots < 1 || nslots > h->hist_depth) return fail(h, TFG_ERR_ARG, "band series: slot count outside 1..hist_depth");
+  HIPCHK(h, hipSetDevice(h->device));
+  const int K = h->n_catch * b->n_bands;
+  const bool planes = sum || count;               // without them one cells-only launch, no plane read
+  const int NB = planes ? band_batch(K) : 0;
+  const int blocks = band_blocks(h->n, K);
+  const int row_sum = NB * K, row_int = NB * K + K;
+  if (sum) HIPCHK(h, h->band_part_sum.reserve((size_t)blocks * row_sum * 8));
+  HIPCHK(h, h->band_part_int.reserve((size_t)blocks * (band_batch(K) * K + K) * 4));
+  if (!out_on_device) {
+    if (sum) HIPCHK(h, h->band_out_sum.reserve((size_t)h->hist_depth * K * 8));
+    HIPCHK(h, h->band_out_int.reserve(((size_t)h->hist_depth * K + K) * 8));
+  }
+  double* dsum = out_on_device ? sum : (double*)h->band_out_sum;
+  int64_t* dcount = out_on_device ? count : (int64_t*)h->band_out_int;
+  int64_t* dcells = out_on_device ? cells : (int64_t*)h->band_out_int + (int64_t)h->hist_depth * K;
+  int fdt = 0;
+  const void* plane = field_ptr(h, field, 0, &fdt);  // slot 0's plane of the field, engine type
+  const int64_t stride = (int64_t)kNumHist * h->n_pad;
+  const size_t lds = band_lds_bytes(NB, K);
+  const int step = planes ? NB : nslots;  // the cells-only call: one trip
+  for (int j0 = 0; j0 < nslots; j0 += step) {
+    const int nb = planes ? std::min(NB, nslots - j0) : 1;
+    const int slot0 = (hist0 + j0) % h->hist_depth;
+    const int what = (sum ? kBandSum : 0) | (count ? kBandCount : 0) | (cells && j0 == 0 ? kBandCells : 0);
+    by_type(h->engine, [&](auto t) {
+      using R = typename decltype(t)::type;
+      auto launch = [&](auto kern) {
+        hipLaunchKernelGGL(kern, blocks, kBlock, lds, h->stream, (const R*)plane, stride, h->hist_depth, slot0, nb,
+                           h->catch_id, (const R*)h->stat.bytes(), edges, b->n_bands, b->threshold, what, h->n, K,
+                           h->band_part_sum, h->band_part_int);
+      };
+      auto with_nb = [&](auto c) {
+        constexpr bool C = decltype(c)::value;
+        switch (NB) {
+          case 8: launch(k_band_series<R, C, 8>); break;
+          case 4: launch(k_band_series<R, C, 4>); break;
+          case 2: launch(k_band_series<R, C, 2>); break;
+          default: launch(k_band_series<R, C, 0>); break;
+        }
+      };
+      if (h->catch_id) with_nb(std::true_type{});
+      else with_nb(std::false_type{});
+    });
+    HIPCHK(h, hipGetLastError());
+    const int nent = nb * K;
+    if (sum) {
+      hipLaunchKernelGGL(k_series_reduce, (nent + 15) / 16, kBlock, 0, h->stream, h->band_part_sum, blocks, row_sum, nent,
+                         dsum + (int64_t)j0 * K);
+      HIPCHK(h, hipGetLastError());
+    }
+    if (count) {
+      hipLaunchKernelGGL(k_band_reduce_int, (nent + 15) / 16, kBlock, 0, h->stream, h->band_part_int, blocks, row_int, nent,
+                         dcount + (int64_t)j0 * K);
+      HIPCHK(h, hipGetLastError());
+    }
+    if (what & kBandCells) {
+      hipLaunchKernelGGL(k_band_reduce_int, (K + 15) / 16, kBlock, 0, h->stream, h->band_part_int + row_sum, blocks, row_int,
+                         K, dcells);
+      HIPCHK(h, hipGetLastError());
+    }
+  }
+  if (!out_on_device) {
+    if (sum) HIPCHK(h, hipMemcpyAsync(sum, dsum, (size_t)nslots * K * 8, hipMemcpyDeviceToHost, h->stream));
+    if (count) HIPCHK(h, hipMemcpyAsync(count, dcount, (size_t)nslots * K * 8, hipMemcpyDeviceToHost, h->stream));
+    if (cells) HIPCHK(h, hipMemcpyAsync(cells, dcells, (size_t)K * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
   }
   return TFG_OK;

@@ -70,6 +70,12 @@ class TfgForcingGrid(ctypes.Structure):
                 ("row0", ctypes.c_int64)]
 
 
+class TfgBands(ctypes.Structure):
+    """tfg_bands: the elevation bands of tfg_band_series (`edges`: a host array of n_bands + 1 doubles)."""
+    _fields_ = [("n_bands", ctypes.c_int32), ("pad", ctypes.c_int32), ("edges", ctypes.POINTER(ctypes.c_double)),
+                ("threshold", ctypes.c_double)]
+
+
 class TfgCellStats(ctypes.Structure):
     """tfg_cell_stats: the accumulators of tfg_cell_aggregate (device pointers, or None)."""
     _fields_ = [("sum", ctypes.c_void_p), ("vmax", ctypes.c_void_p), ("vmin", ctypes.c_void_p),
@@ -130,6 +136,7 @@ def load() -> ctypes.CDLL:
         "tfg_get_diag": ([vp, dp, i32], i32),
         "tfg_reset_diag": ([vp], i32),
         "tfg_catchment_series": ([vp, i32, i32, i32, vp, i32], i32),
+        "tfg_band_series": ([vp, i32, i32, i32, ctypes.POINTER(TfgBands), vp, vp, vp, i32], i32),
         "tfg_cell_aggregate": ([vp, i32, i32, i32, ctypes.POINTER(TfgCellStats), i32], i32),
         "tfg_sync": ([vp], i32),
         "tfg_fill_synthetic": ([vp, ctypes.c_uint64, i64, i64, ctypes.POINTER(ctypes.c_float), i32], i32),
@@ -327,5 +334,5 @@ def exported_symbols() -> list[str]:
         "tfg_update", "tfg_update_many", "tfg_conduction_edges", "tfg_conduction_update", "tfg_conduction_off",
         "tfg_nan_safe_launches", "tfg_set_step_form", "tfg_set_flux", "tfg_set_split", "tfg_join", "tfg_get_split",
         "tfg_selftest_powers", "tfg_catchment_series", "tfg_set_catchment_forcing", "tfg_cell_aggregate",
-        "tfg_set_gridded_forcing",
+        "tfg_set_gridded_forcing", "tfg_band_series",
     ) if hasattr(L, n)]

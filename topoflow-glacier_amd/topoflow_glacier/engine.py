@@ -109,6 +109,7 @@ class GlacierEngine:
                 self._catch_cells = None  # catchment_cells() counts the new raster
             if name in ("catch_id", "elev"):
                 self._catch_elev = None  # catchment_mean_elevation() sums the new raster
+                self._hypsometry = None  # hypsometry() counts the new rasters
             code = {4: nat.F32, 8: nat.F64}[t.element_size()] if name != "catch_id" else nat.I32
             if t.numel() != self.n:
                 raise ValueError(f"{name}: {t.numel()} values for {self.n} cells")
@@ -120,6 +121,7 @@ class GlacierEngine:
             return
         if name in ("catch_id", "elev"):
             self._catch_elev = None  # catchment_mean_elevation() sums the new raster
+            self._hypsometry = None  # hypsometry() counts the new rasters
         if name == "catch_id":
             self._catch_cells = None  # catchment_cells() counts the new raster
             a = np.ascontiguousarray(np.broadcast_to(np.asarray(values, dtype=np.int32), (self.n,)))
@@ -393,6 +395,7 @@ class GlacierEngine:
                                               d.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), self.n_frames))
         self.step_index = 0
         self._catch_elev = None  # the generator writes the elevation raster
+        self._hypsometry = None
 
     # -- time stepping ------------------------------------------------------------
     _UBLOCK = 512  # steps of uniforms computed at once for short runs
@@ -712,6 +715,80 @@ class GlacierEngine:
             cells = self.catchment_cells()
             res = np.where(cells > 0, res / np.maximum(cells, 1), 0.0)
         return res
+
+    def band_series(self, name: str, edges, first: int | None = None, count: int | None = None,
+                    threshold: float = 0.0, want=("sum", "count", "cells"), out=None) -> dict:
+        """Per catchment and elevation band, an output field in `count`
+        consecutive history slots from slot `first`, following the ring
+        (tfg_band_series: reduced on the device, the planes stay there).  A
+        cell is in band k iff edges[k] <= elev < edges[k+1], with elev as the
+        engine holds it; a cell outside the edges, or of NaN elevation, is in
+        no band.  Returns a dict of the arrays named in `want`:
+
+            "sum"    [count][n_catch][n_bands] float64   the band's sum
+            "count"  [count][n_catch][n_bands] int64     its cells with value > threshold
+            "cells"  [n_catch][n_bands] int64            its cells (the hypsometry)
+
+        Defaults for `first` and `count`: catchment_series's (the slots of the
+        last min(step_index, hist_depth) steps, in step order).  With only
+        "cells" wanted no plane is read.
+
+        `out` may be a dict of contiguous torch CUDA tensors on the engine's
+        device, float64 for "sum" and int64 for "count" and "cells", of
+        exactly those element counts; `want` is then its keys, the call is
+        queued on the engine's stream without a host wait under
+        catchment_series's stream rule (torch's current stream is drained
+        first; the caller sync()s before reading), and `out` is returned."""
+        e = np.ascontiguousarray(np.asarray(edges, dtype=np.float64).reshape(-1))
+        nb = e.size - 1
+        if nb < 1:
+            raise ValueError("band_series: need at least two edges")
+        if count is None:
+            count = max(min(self.step_index, self.hist_depth), 1)
+        if first is None:
+            first = (self.step_index - count) % self.hist_depth if self.step_index else 0
+        first, count = int(first), int(count)
+        fid = nat.FIELD[name]
+        names = ("sum", "count", "cells")
+        want = tuple(out) if out is not None else ((want,) if isinstance(want, str) else tuple(want))
+        if not want or any(w not in names for w in want):
+            raise ValueError(f"band_series: want some of {names}, not {want!r}")
+        bands = nat.TfgBands(nb, 0, e.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), float(threshold))
+        shapes = {"sum": (max(count, 1), self.n_catch, nb), "count": (max(count, 1), self.n_catch, nb),
+                  "cells": (self.n_catch, nb)}
+        if out is not None:
+            import torch
+
+            kinds = {"sum": torch.float64, "count": torch.int64, "cells": torch.int64}
+            for w, t in out.items():
+                numel = (max(count, 0) if w != "cells" else 1) * self.n_catch * nb
+                if not (getattr(t, "is_cuda", False) and t.is_contiguous() and t.dtype == kinds[w]
+                        and t.numel() == numel and t.device.index == self.device):
+                    raise ValueError(f"out[{w!r}]: need a contiguous {kinds[w]} CUDA tensor of {numel} elements "
+                                     f"on cuda:{self.device}")
+            torch.cuda.current_stream(self.torch_device).synchronize()  # `out` may still be in use on torch's stream
+            ptr = {w: ctypes.c_void_p(out[w].data_ptr()) if w in out else None for w in names}
+            self._chk(self.lib.tfg_band_series(self.h, fid, first, count, ctypes.byref(bands), ptr["sum"], ptr["count"],
+                                               ptr["cells"], 1))
+            return out
+        res = {w: np.empty(shapes[w], dtype=np.float64 if w == "sum" else np.int64) for w in want}
+        ptr = {w: res[w].ctypes.data_as(ctypes.c_void_p) if w in res else None for w in names}
+        self._chk(self.lib.tfg_band_series(self.h, fid, first, count, ctypes.byref(bands), ptr["sum"], ptr["count"],
+                                           ptr["cells"], 0))
+        return res
+
+    def hypsometry(self, edges) -> np.ndarray:
+        """[n_catch][n_bands] int64 cells of each catchment and elevation band
+        of this shard (band_series's "cells" alone: no plane is read), cached
+        per set of edges until elev or catch_id is set again."""
+        e = np.asarray(edges, dtype=np.float64).reshape(-1)
+        key = e.tobytes()
+        cache = getattr(self, "_hypsometry", None)
+        if cache is None or cache[0] != key:
+            cells = self.band_series("M_total", e, first=0, count=1, want=("cells",))["cells"]
+            cells.setflags(write=False)
+            self._hypsometry = cache = (key, cells)
+        return cache[1]
 
     def cell_aggregate(self, name: str, first: int | None = None, count: int | None = None, *, sum=None, max=None,
                        min=None, above=None, threshold: float = 0.0, init: bool = False) -> None:

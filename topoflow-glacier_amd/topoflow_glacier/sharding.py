@@ -72,6 +72,33 @@ def allreduce_catchment_series(series: np.ndarray, group=None, device=None) -> n
     return t.cpu().numpy()
 
 
+def allreduce_band_series(sum=None, count=None, cells=None, group=None, device=None) -> tuple:
+    """Combine per-shard band series (GlacierEngine.band_series: sums, counts
+    above the threshold, cells per band): the sums in one float64 SUM
+    all-reduce, counts and cells together in one int64 SUM all-reduce (exact,
+    where a float64 reduction of counts would round past 2^53); copies when no
+    process group is up.  None stays None.  A band's mean or covered fraction
+    over shards comes from the reduced arrays, never from the shards' own."""
+    import torch
+    import torch.distributed as dist
+
+    s = None if sum is None else allreduce_catchment_series(sum, group=group, device=device)
+    ints = [None if a is None else np.ascontiguousarray(a, dtype=np.int64) for a in (count, cells)]
+    if not (dist.is_available() and dist.is_initialized()):
+        return (s, *(None if a is None else a.copy() for a in ints))
+    have = [a for a in ints if a is not None]
+    if have:
+        dev = device if device is not None else ("cuda" if dist.get_backend(group) == "nccl" else "cpu")
+        t = torch.from_numpy(np.concatenate([a.reshape(-1) for a in have])).to(dev)
+        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+        flat, pos = t.cpu().numpy(), 0
+        for i, a in enumerate(ints):
+            if a is not None:
+                ints[i] = flat[pos:pos + a.size].reshape(a.shape).copy()
+                pos += a.size
+    return (s, *ints)
+
+
 def allreduce_catchment_elevation(sum, cells, group=None, device=None) -> np.ndarray:
     """The global reference elevation z_ref [n_catch] of
     GlacierEngine.set_catchment_forcing from the shards' per-catchment
