@@ -406,6 +406,126 @@ def gpu_run_fields(cfg: dict, static: dict, forcing: dict, ny: int, nx: int, eng
         eng.close()
 
 
+# ---------------------------------------------------------------- days since snowfall, at every step
+INPUT_ORDER = ("P_air", "Hum_sp", "P", "T_air", "uz")  # tfg_set_inputs / tfg_update order
+
+
+def ring_as_slots(ring: np.ndarray, steps_done: int) -> np.ndarray:
+    """The oracle's ring [ncell][ring_len] (newest last) as the engine's slots
+    [ring_len][ncell]: ring[:, L-1-j] holds step steps_done-1-j, which the
+    engine keeps in slot (steps_done-1-j) mod L."""
+    L = ring.shape[1]
+    out = np.empty((L, ring.shape[0]))
+    for j in range(L):
+        out[(steps_done - 1 - j) % L] = ring[:, L - 1 - j]
+    return out
+
+
+def oracle_days_per_step(cfg: dict, static: dict, forcing: dict, nsteps: int, ring_at=(), inject=None):
+    """The numpy oracle's days since major snowfall after every step: n
+    [nsteps][ncell] (m.n recorded after each step, tfg_oracle.py:476-483), the
+    float64 window sum tot [nsteps][ncell] it decided on, and rings[k] =
+    the ring as engine slots [ring_len][ncell] after k steps, for k in ring_at.
+    inject = {steps done: [(slot, values [ncell]), ...]} overwrites window
+    slots (engine numbering) before the step that follows."""
+    m = O.OracleGrid(cfg, **{k: np.asarray(static[k], np.float64) for k in STATIC_KEYS})
+    jd, _, _, tsn = O.oracle_clock(cfg["start_time"], cfg["dt"], nsteps, cfg["lon"])
+    L = m.ring.shape[1]
+    n, tot, rings = np.empty((nsteps, m.n_cell)), np.empty((nsteps, m.n_cell)), {}
+    with np.errstate(all="ignore"):  # the edge cases feed it NaN, inf and negative snowfall
+        for k in range(nsteps):
+            for slot, values in (inject or {}).get(k, ()):
+                m.ring[:, L - 1 - ((k - 1 - slot) % L)] = values
+            m.step(*(np.asarray(forcing[v][k], np.float64) for v in ("P", "T_air", "Hum_sp", "P_air", "uz")), jd[k], tsn[k])
+            n[k], tot[k] = m.n, np.sum(m.ring, axis=1)
+            if k + 1 in ring_at:
+                rings[k + 1] = ring_as_slots(m.ring, k + 1)
+    return SimpleNamespace(n=n, tot=tot, rings=rings, dpd=m.days_per_dt)
+
+
+def setup_engine(eng, static: dict) -> None:
+    for k in ("elev", "slope", "aspect"):
+        eng.set_field(k, static[k])
+    for k in ("h_snow", "h_ice", "h_swe", "h_iwe"):
+        eng.set_field(k, static["h0_" + k[2:]])
+    eng.init_state()
+
+
+def read_window(eng) -> np.ndarray:
+    """Every snowfall-window slot [ring_len][ncell], in metres (TFG_ST_WINDOW)."""
+    return np.stack([eng.get_field("window", index=j) for j in range(eng.ring_len)])
+
+
+def gpu_days_per_launch(cfg: dict, static: dict, forcing: dict, ny: int, nx: int, engine: str, launches,
+                        window_at=(), inject=None, nan_safe: bool = False):
+    """Run the launches (steps per launch, in order; each run() is one kernel
+    launch, fuse = the longest) on per-step forcing and read n (TFG_ST_NDAYS)
+    after each.  Returns n [n_launches][ncell], done [n_launches] (steps done
+    after each launch), windows[k] = slots [ring_len][ncell] after k steps for
+    k in window_at (launch ends), and ns [n_launches], the engine's count of
+    NaN-safe launches after each.  inject = {steps done: [(slot, values), ...]}
+    sets window slots (set_field: a host array or a device tensor) before the
+    launch that starts there.  nan_safe: the fp32 engine's NaN-safe step form
+    in every launch (set_step_form), whatever the data."""
+    launches = [int(c) for c in launches]
+    nsteps, n = sum(launches), ny * nx
+    eng = make_engine(cfg, ny, nx, engine, n_frames=nsteps, hist_depth=1, fuse_steps=max(launches))
+    try:
+        setup_engine(eng, static)
+        if nan_safe:
+            eng.set_step_form(True)
+        for k in range(nsteps):
+            eng.set_inputs(np.stack([np.asarray(forcing[v][k], np.float64).reshape(n) for v in INPUT_ORDER]), k)
+        out_n, done, windows, ns = [], [], {}, []
+        k0 = 0
+        for c in launches:
+            for slot, values in (inject or {}).get(k0, ()):
+                eng.set_field("window", values, index=slot)
+            eng.run(c, frames=np.arange(k0, k0 + c, dtype=np.int32))
+            eng.sync()
+            k0 += c
+            out_n.append(eng.get_field("n"))
+            done.append(k0)
+            ns.append(eng.nan_safe_launches())
+            if k0 in window_at:
+                windows[k0] = read_window(eng)
+        return SimpleNamespace(n=np.stack(out_n), done=np.array(done), windows=windows, ns=np.array(ns))
+    finally:
+        eng.close()
+
+
+def gpu_days_one_cell(cfg: dict, static: dict, forcing: dict, cell: int, nsteps: int, kernel: str, launches=None):
+    """The same for a 1 x 1 fp64 engine holding cell `cell`, through one of the
+    one-cell kernels: "k_cell" (update_io, one step per call), "k_cell_many"
+    (update_many) or "k_cell_run" (run(); `launches` as above).  Returns
+    (n [n_calls], steps done after each call, final slots [ring_len])."""
+    from topoflow_glacier.engine import update_many
+
+    one = {k: np.asarray(v, np.float64)[cell:cell + 1] for k, v in static.items()}
+    if kernel == "k_cell_run":
+        f1 = {k: np.asarray(v, np.float64)[:nsteps, cell:cell + 1] for k, v in forcing.items()}
+        r = gpu_days_per_launch(cfg, one, f1, 1, 1, "float64", launches or [1] * nsteps, window_at=(nsteps,))
+        return r.n[:, 0], r.done, r.windows[nsteps][:, 0]
+    eng = make_engine(cfg, 1, 1, "float64", n_frames=1, hist_depth=1)
+    try:
+        setup_engine(eng, one)
+        if kernel == "k_cell_many":
+            from topoflow_glacier.bmi import bmi_topoflow_glacier as B
+
+            eng.set_stream(B._shared_stream(0))
+        out, ns_ = np.empty((8, 1)), []
+        for k in range(nsteps):
+            vals = np.array([[forcing[v][k][cell]] for v in INPUT_ORDER], dtype=np.float64)
+            if kernel == "k_cell":
+                eng.update_io(vals, out)
+            else:
+                update_many([eng], [vals], [out])
+            ns_.append(eng.get_field("n")[0])
+        return np.array(ns_), np.arange(1, nsteps + 1), read_window(eng)[:, 0]
+    finally:
+        eng.close()
+
+
 def synthetic_inputs(seed: int, ny: int, nx: int, n_frames: int, row0: int = 0):
     from topoflow_glacier.synthetic import diurnal_table, synthetic_cells
 
