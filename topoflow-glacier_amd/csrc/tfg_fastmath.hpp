@@ -205,11 +205,16 @@ TFG_FM_HD inline double exp_p(double x) {
 }
 
 // exp(c + s) / exp(c) for |s| <= 0.41 (the flux form's lhc / p0 factor,
-// exp(-M g elev / (R T_K)) with its exponent y in [-0.755, 0.065] centred at
-// c = kP0Center, so elevations up to ~5 km at any air temperature): a degree-8
-// polynomial in s with no reduction (scripts/fit_exp.py 8 on [-0.41, 0.41]:
-// 5.1e-12 relative), 8 VALU for exp_p's 12.  The caller folds exp(c) into its
-// constant factor and takes exp_p for a wave with a lane outside the range.
+// exp(y) with y = +M g elev / (R T_K) >= 0, since lhc / p0 grows with height,
+// and s = y - c, c = kP0Center): a degree-8 polynomial in s with no reduction
+// (scripts/fit_exp.py 8 on [-0.41, 0.41]: 5.1e-12 relative), 8 VALU for
+// exp_p's 12.  The caller folds exp(c) into its constant factor; a lane whose s
+// is outside the range takes exp_p, each lane by its own s (cell_step_fast).
+// With c = -0.345 the range is y in [-0.755, 0.065], i.e. elevations up to
+// ~500 m only (y = 0.065 at elev / T_K = 1.9 m/K): the centre was meant for a
+// negative exponent, and every higher cell runs exp_p.  The results are
+// right either way; c = +0.345 would cover ~5 km, and would move the last
+// bits of Qe in every cell that then changes function.
 constexpr double kP0Center = -0.345;
 constexpr double kP0Half = 0.41;
 TFG_FM_HD inline double exp_near(double s) {

@@ -1178,10 +1178,19 @@ __device__ inline void cell_step_fast(const DevParams& p, const CellStaticF& g, 
     const double ded = e64 * (1.0 - tfg_fm::exp_p(x_es));
     // lhc / p0 = exp(y), y = ek ln2 / T_K, as exp(c) exp(y - c) with exp(c) in d_qe
     const double s0 = fma((double)g.ek * 0.69314718055994531, rcp_nr1(Td + 273.15), -tfg_fm::kP0Center);
+    // The branches are wave-wide, the choice of the function is the lane's own: a lane inside
+    // exp_near's range takes exp_near whatever its neighbours do (the two differ in the last bits,
+    // and a cell's result must not depend on which cells share its wave;
+    // tests/test_gpu_step_terms.py).  A wave wholly outside the range costs what it did.
+    const bool far = !(fabs(s0) <= tfg_fm::kP0Half);
     double p0f;
-    if (__builtin_expect(__any(!(fabs(s0) <= tfg_fm::kP0Half)), 0)) {
+    if (__builtin_expect(__any(far), 0)) {
       TFG_FM_RARE();
       p0f = tfg_fm::exp_p(s0);
+      if (__any(!far)) {
+        TFG_FM_RARE();
+        p0f = far ? p0f : tfg_fm::exp_near(s0);
+      }
     } else {
       p0f = tfg_fm::exp_near(s0);
     }
