@@ -410,6 +410,49 @@ typedef struct tfg_bands {
 int tfg_band_series(tfg_handle* h, int field, int hist0, int nslots, const tfg_bands* b,
                     double* sum, int64_t* count, int64_t* cells, int out_on_device);
 
+/* Per-node sums and counts of one output field over history slots on a regular
+ * coarse grid, reduced on the device: the model's outputs on the grid its
+ * forcing came from (tfg_set_gridded_forcing), per step.  `g` is that call's
+ * tfg_forcing_grid; g->method is not read: a cell always belongs to its
+ * NEAREST node, by exactly the rule of TFG_REGRID_NEAREST.  For local cell
+ * (r, c), with R = g->row0 + r, in fp64 without contraction, ties going up:
+ *   J = floor(min(max(y0 + sy R, 0), gny - 1) + 0.5)        (I alike, from c)
+ * so the call is the exact adjoint of nearest-neighbour forcing: the cells
+ * that receive node (J, I)'s forcing are the cells whose outputs are summed
+ * into (J, I), the cells clamped onto an edge node included.  J depends on the
+ * row alone and I on the column alone, both monotonically: a node owns a
+ * rectangle of rows(J) x cols(I) cells, and no id raster is read.
+ *   sum  [nslots][gny][gnx] fp64   the sum of field[slot (hist0 + j) %
+ *        hist_depth][cell] over the node's cells of this shard, accumulated
+ *        in fp64, unscaled
+ *   count[nslots][gny][gnx] int64  the number of those cells with
+ *        (double)value > threshold; a NaN value is never counted
+ *   cells        [gny][gnx] int64  the node's cells of this shard, rows(J)
+ *        cols(I): independent of the field
+ * A NULL pointer leaves that output out; at least one is set.  With sum ==
+ * NULL && count == NULL no history plane is read (field, hist0 and nslots are
+ * still validated).  Every entry is written; a node without cells reads 0 in
+ * all three.  Row-block shards that share a node row each hold a partial: the
+ * whole grid's arrays are the shards' sums.  No floating-point atomics and no
+ * dependence on dispatch order: two calls give the same bits, and a (slot,
+ * node) entry is the same bit for bit whichever other slots share the call,
+ * wherever in a batch it sits and wherever the outputs live.  A NaN value
+ * reaches exactly the sum entry of its own (slot, node).
+ * out_on_device == 0: the outputs are host memory and the call blocks.
+ * Otherwise they are device pointers and the call is queued on the handle's
+ * stream (after the second part of a split launch), without a host wait.
+ * TFG_ERR_ARG, with nothing written: a null handle or g; all three outputs
+ * NULL; gny or gnx < 1 or gny * gnx >= 2^29; a non-finite y0, x0, sy or sx;
+ * row0 < 0; a NaN threshold with count set; a field that is not one of the
+ * six history fields; hist0 or nslots out of range (tfg_catchment_series's
+ * rule).
+ * Replaces: the per-step get_value loop of a coupled caller of the reference
+ * that bins runoff, melt, snow depth or snow cover onto the atmospheric
+ * model's grid; the reference has one cell per catchment and no counterpart
+ * of its own (the rule is restated in numpy by tests/coarse_ref.py). */
+int tfg_coarse_series(tfg_handle* h, int field, int hist0, int nslots, const tfg_forcing_grid* g, double threshold,
+                      double* sum, int64_t* count, int64_t* cells, int out_on_device);
+
 /* Per-cell time aggregates of one output field over history slots, folded on
  * the device.  For every cell i < ny*nx, with v_j = field[slot (hist0 + j) %
  * hist_depth][i] in the engine's element type, j = 0 .. nslots-1 in that

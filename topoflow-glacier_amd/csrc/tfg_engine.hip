@@ -499,6 +499,7 @@ __global__ void k_terrain(const R* __restrict__ elev, const double* __restrict__
 #include "tfg_bands.hpp"  // per-catchment, per-elevation-band sums and counts of history planes (tfg_band_series)
 #include "tfg_aggregate.hpp"  // per-cell time aggregates of history planes (tfg_cell_aggregate)
 #include "tfg_forcing.hpp"  // forcing spread over the grid: per catchment (tfg_set_catchment_forcing), regridded (tfg_set_gridded_forcing)
+#include "tfg_coarse.hpp"  // per-node sums and counts of history planes on a coarse grid (tfg_coarse_series)
 
 // tfg_set_inputs / tfg_get_outputs: the per-step BMI traffic of one call each.
 // src [5][n]: P_air, Hum_sp, P, T_air, uz (BMI order) -> frame planes.
@@ -736,6 +737,16 @@ struct tfg_handle {
   Dev<int32_t> band_part_int;    // [band_blocks][band_batch * K + K]: counts, then cells
   Dev<double> band_out_sum;      // [hist_depth][K]
   Dev<int64_t> band_out_int;     // [hist_depth][K] counts, then [K] cells
+  // tfg_coarse_series, allocated on first use: the tables of the last grid (coarse_plan, kept while the
+  // grid's bytes stay the same), the workgroups' partials and a host call's copy of one batch
+  Dev<int32_t> coarse_tab;
+  Dev<double> coarse_part_sum;   // [nseg][kCoarseBatch][P]
+  Dev<int32_t> coarse_part_cnt;  // [nseg][kCoarseBatch][P]
+  Dev<double> coarse_out_sum;    // [kCoarseBatch][gny * gnx]
+  Dev<int64_t> coarse_out_int;   // [kCoarseBatch][gny * gnx] counts, then [gny * gnx] cells
+  tfg_forcing_grid coarse_grid{};  // the grid coarse_tab holds (method and pad zeroed), while coarse_valid
+  CoarsePlan coarse;
+  bool coarse_valid = false;
   Dev<float> d_diurnal;
   Dev<int32_t> d_flag;
   // tfg_step's staged steps: [nsteps] tfg_uniforms, then the [nsteps] StepAddr
@@ -1990,6 +2001,136 @@ int tfg_band_series(tfg_handle* h, int field, int hist0, int nslots, const tfg_b
     if (cells) HIPCHK(h, hipMemcpyAsync(cells, dcells, (size_t)K * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
   }
+  return TFG_OK;
+}
+
+extern "C++" {  // a template below
+namespace {
+
+// The tables of grid g on the device (coarse_plan): kept while the calls pass the same grid.
+int coarse_prepare(tfg_handle* h, const tfg_forcing_grid& g) {
+  tfg_forcing_grid key = g;
+  key.method = 0;  // not read: the key rule is the nearest node's
+  key.pad = 0;
+  if (h->coarse_valid && !std::memcmp(&key, &h->coarse_grid, sizeof key)) return TFG_OK;
+  h->coarse_valid = false;
+  std::vector<int32_t> tab;
+  const CoarsePlan p = coarse_plan(h->ny, h->nx, key, 16 / (int)h->rsz, tab);
+  if ((int64_t)p.nseg * p.ntiles > INT32_MAX) return fail(h, TFG_ERR_ARG, "coarse series: too many row segments x column tiles");
+  const size_t bytes = tab.size() * sizeof(int32_t);
+  StageRing::Slot* s = nullptr;  // through the pinned ring: one queued copy, no host wait
+  HIPCHK(h, h->in_ring.acquire(bytes, false, &s));
+  std::memcpy(s->host.ptr, tab.data(), bytes);
+  HIPCHK(h, h->coarse_tab.reserve(bytes));
+  HIPCHK(h, hipMemcpyAsync(h->coarse_tab.ptr, s->host.ptr, bytes, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, StageRing::commit(*s, h->stream));
+  h->coarse = p;
+  h->coarse_grid = key;
+  h->coarse_valid = true;
+  return TFG_OK;
+}
+
+// out[nb][gny][gnx] from a batch's partials, by the plan's threads per entry.
+template <class T, class O>
+int coarse_fold(tfg_handle* h, const T* part, int nb, const tfg_forcing_grid& g, O* out) {
+  const CoarsePlan& p = h->coarse;
+  const int32_t* tab = h->coarse_tab;
+  const int64_t nent = (int64_t)nb * g.gny * g.gnx, per = kBlock / p.fold_th, blocks = (nent + per - 1) / per;
+  if (blocks > INT32_MAX) return fail(h, TFG_ERR_ARG, "coarse series: too many nodes for this geometry's fold");
+  auto launch = [&](auto kern) {
+    hipLaunchKernelGGL(kern, (int)blocks, kBlock, 0, h->stream, part, nb, g.gny, g.gnx, p.P, tab + p.o_segj, tab + p.o_pairi, out);
+  };
+  switch (p.fold_th) {
+    case 1: launch(k_coarse_fold<T, O, 1>); break;
+    case 16: launch(k_coarse_fold<T, O, 16>); break;
+    default: launch(k_coarse_fold<T, O, 256>); break;
+  }
+  HIPCHK(h, hipGetLastError());
+  return TFG_OK;
+}
+
+}  // namespace
+}  // extern "C++"
+
+int tfg_coarse_series(tfg_handle* h, int field, int hist0, int nslots, const tfg_forcing_grid* g, double threshold,
+                      double* sum, int64_t* count, int64_t* cells, int out_on_device) {
+  if (int rc_ = api_sync(h)) return rc_;  // after a split launch's second part
+  if (!h) return fail(nullptr, TFG_ERR_ARG, "null handle");
+  if (!g) return fail(h, TFG_ERR_ARG, "coarse series: null grid");
+  if (!sum && !count && !cells) return fail(h, TFG_ERR_ARG, "coarse series: no output requested");
+  if (g->gny < 1 || g->gnx < 1) return fail(h, TFG_ERR_ARG, "coarse series: gny and gnx must be >= 1");
+  if ((int64_t)g->gny * g->gnx >= ((int64_t)1 << 29))  // tfg_set_gridded_forcing's limit
+    return fail(h, TFG_ERR_ARG, "coarse series: gny * gnx must stay under 2^29");
+  if (!std::isfinite(g->y0) || !std::isfinite(g->x0) || !std::isfinite(g->sy) || !std::isfinite(g->sx))
+    return fail(h, TFG_ERR_ARG, "coarse series: y0, x0, sy and sx must be finite");
+  if (g->row0 < 0) return fail(h, TFG_ERR_ARG, "coarse series: row0 must be >= 0");
+  if (count && threshold != threshold) return fail(h, TFG_ERR_ARG, "coarse series: NaN threshold");
+  if (!is_hist_field(field))
+    return fail(h, TFG_ERR_ARG, "coarse series: field " + std::to_string(field) +
+                                    " is not a history field (h_snow, SM, h_ice, IM, M_total, RH)");
+  if (hist0 < 0 || hist0 >= h->hist_depth) return fail(h, TFG_ERR_ARG, "coarse series: first history slot out of range");
+  if (nslots < 1 || nslots > h->hist_depth) return fail(h, TFG_ERR_ARG, "coarse series: slot count outside 1..hist_depth");
+  HIPCHK(h, hipSetDevice(h->device));
+  if (int rc = coarse_prepare(h, *g)) return rc;
+  const CoarsePlan& p = h->coarse;
+  const int32_t* tab = h->coarse_tab;
+  const size_t nodes = (size_t)g->gny * (size_t)g->gnx;
+  const size_t part_len = (size_t)p.nseg * kCoarseBatch * p.P;
+  if (sum) HIPCHK(h, h->coarse_part_sum.reserve(part_len * 8));
+  if (count) HIPCHK(h, h->coarse_part_cnt.reserve(part_len * 4));
+  if (!out_on_device) {
+    if (sum) HIPCHK(h, h->coarse_out_sum.reserve(kCoarseBatch * nodes * 8));
+    HIPCHK(h, h->coarse_out_int.reserve((kCoarseBatch * nodes + nodes) * 8));
+  }
+  if (cells) {  // rows(J) cols(I): no plane is read
+    int64_t* dcells = out_on_device ? cells : (int64_t*)h->coarse_out_int + kCoarseBatch * nodes;
+    hipLaunchKernelGGL(k_coarse_cells, (int)std::min<size_t>((nodes + kBlock - 1) / kBlock, 4096), kBlock, 0, h->stream,
+                       tab + p.o_rows, tab + p.o_cols, g->gny, g->gnx, dcells);
+    HIPCHK(h, hipGetLastError());
+    if (!out_on_device) HIPCHK(h, hipMemcpyAsync(cells, dcells, nodes * 8, hipMemcpyDeviceToHost, h->stream));
+  }
+  if (sum || count) {
+    int fdt = 0;
+    const void* plane = field_ptr(h, field, 0, &fdt);  // slot 0's plane of the field, engine type
+    const int64_t stride = (int64_t)kNumHist * h->n_pad;
+    const int v = 16 / (int)h->rsz;
+    const bool vec = h->nx % v == 0 && (uintptr_t)plane % 16 == 0 && (stride * (int64_t)h->rsz) % 16 == 0;
+    for (int j0 = 0; j0 < nslots; j0 += kCoarseBatch) {
+      const int nb = std::min(kCoarseBatch, nslots - j0);
+      const int slot0 = (hist0 + j0) % h->hist_depth;
+      by_type(h->engine, [&](auto t) {
+        using R = typename decltype(t)::type;
+        auto launch = [&](auto kern) {
+          hipLaunchKernelGGL(kern, p.nseg * p.ntiles, kBlock, 0, h->stream, (const R*)plane, stride, h->hist_depth, slot0, nb,
+                             (int)h->nx, tab + p.o_seg, tab + p.o_pcol, p.ntiles, p.P, threshold,
+                             (double*)h->coarse_part_sum, (int32_t*)h->coarse_part_cnt);
+        };
+        auto with_what = [&](auto vc) {
+          constexpr bool VEC = decltype(vc)::value;
+          if (sum && count) launch(k_coarse_series<R, VEC, true, true>);
+          else if (sum) launch(k_coarse_series<R, VEC, true, false>);
+          else launch(k_coarse_series<R, VEC, false, true>);
+        };
+        if (vec) with_what(std::true_type{});
+        else with_what(std::false_type{});
+      });
+      HIPCHK(h, hipGetLastError());
+      // a device output takes the batch's rows in place; a host output is copied out batch by batch
+      if (sum) {
+        double* dsum = out_on_device ? sum + (size_t)j0 * nodes : (double*)h->coarse_out_sum;
+        if (int rc = coarse_fold(h, (const double*)h->coarse_part_sum, nb, *g, dsum)) return rc;
+        if (!out_on_device)
+          HIPCHK(h, hipMemcpyAsync(sum + (size_t)j0 * nodes, dsum, (size_t)nb * nodes * 8, hipMemcpyDeviceToHost, h->stream));
+      }
+      if (count) {
+        int64_t* dcount = out_on_device ? count + (size_t)j0 * nodes : (int64_t*)h->coarse_out_int;
+        if (int rc = coarse_fold(h, (const int32_t*)h->coarse_part_cnt, nb, *g, dcount)) return rc;
+        if (!out_on_device)
+          HIPCHK(h, hipMemcpyAsync(count + (size_t)j0 * nodes, dcount, (size_t)nb * nodes * 8, hipMemcpyDeviceToHost, h->stream));
+      }
+    }
+  }
+  if (!out_on_device) HIPCHK(h, hipStreamSynchronize(h->stream));
   return TFG_OK;
 }
 

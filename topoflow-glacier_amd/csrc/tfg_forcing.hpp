@@ -274,8 +274,10 @@ struct RegridAxis {
 };
 
 // Model index k (global) on an axis of m nodes: coordinate o + s k.
+// (Also evaluated on the host, for tfg_coarse_series's tables: the same fp64
+// operations in the same order, without contraction.)
 template <bool BIL>
-__device__ __forceinline__ RegridAxis regrid_axis(double o, double s, int64_t k, int m) {
+__host__ __device__ __forceinline__ RegridAxis regrid_axis(double o, double s, int64_t k, int m) {
 #pragma clang fp contract(off)
   const double t = o + s * (double)k;
   const double tc = fmin(fmax(t, 0.0), (double)(m - 1));

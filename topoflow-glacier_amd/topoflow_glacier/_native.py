@@ -137,6 +137,7 @@ def load() -> ctypes.CDLL:
         "tfg_reset_diag": ([vp], i32),
         "tfg_catchment_series": ([vp, i32, i32, i32, vp, i32], i32),
         "tfg_band_series": ([vp, i32, i32, i32, ctypes.POINTER(TfgBands), vp, vp, vp, i32], i32),
+        "tfg_coarse_series": ([vp, i32, i32, i32, ctypes.POINTER(TfgForcingGrid), ctypes.c_double, vp, vp, vp, i32], i32),
         "tfg_cell_aggregate": ([vp, i32, i32, i32, ctypes.POINTER(TfgCellStats), i32], i32),
         "tfg_sync": ([vp], i32),
         "tfg_fill_synthetic": ([vp, ctypes.c_uint64, i64, i64, ctypes.POINTER(ctypes.c_float), i32], i32),
@@ -334,5 +335,5 @@ def exported_symbols() -> list[str]:
         "tfg_update", "tfg_update_many", "tfg_conduction_edges", "tfg_conduction_update", "tfg_conduction_off",
         "tfg_nan_safe_launches", "tfg_set_step_form", "tfg_set_flux", "tfg_set_split", "tfg_join", "tfg_get_split",
         "tfg_selftest_powers", "tfg_catchment_series", "tfg_set_catchment_forcing", "tfg_cell_aggregate",
-        "tfg_set_gridded_forcing", "tfg_band_series",
+        "tfg_set_gridded_forcing", "tfg_band_series", "tfg_coarse_series",
     ) if hasattr(L, n)]

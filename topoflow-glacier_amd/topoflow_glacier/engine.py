@@ -777,6 +777,70 @@ class GlacierEngine:
                                            ptr["cells"], 0))
         return res
 
+    def coarse_series(self, name: str, grid, first: int | None = None, count: int | None = None,
+                      threshold: float = 0.0, want=("sum", "count", "cells"), out=None) -> dict:
+        """Per node of a regular coarse grid, an output field in `count`
+        consecutive history slots from slot `first`, following the ring
+        (tfg_coarse_series: reduced on the device, the planes stay there).
+        `grid` is a forcing.ForcingGrid, the one set_gridded_forcing takes;
+        its method is not read: a cell belongs to its nearest node (ties go
+        up), so the cells that receive a node's "nearest" forcing are the
+        cells summed into it.  The engine adds its own row0, so row-block
+        shards pass the same grid and each returns its partial
+        (sharding.allreduce_coarse_series).  Returns a dict of the arrays
+        named in `want`:
+
+            "sum"    [count][gny][gnx] float64   the node's sum
+            "count"  [count][gny][gnx] int64     its cells with value > threshold
+            "cells"  [gny][gnx] int64            its cells of this shard
+
+        A node without cells reads 0 in all three.  Defaults for `first` and
+        `count`: band_series's (the slots of the last min(step_index,
+        hist_depth) steps, in step order).  With only "cells" wanted no plane
+        is read.
+
+        `out` may be a dict of contiguous torch CUDA tensors on the engine's
+        device, float64 for "sum" and int64 for "count" and "cells", of
+        exactly those element counts; `want` is then its keys, the call is
+        queued on the engine's stream without a host wait under band_series's
+        stream rule (torch's current stream is drained first; the caller
+        sync()s before reading), and `out` is returned."""
+        gny, gnx = int(grid.gny), int(grid.gnx)
+        if count is None:
+            count = max(min(self.step_index, self.hist_depth), 1)
+        if first is None:
+            first = (self.step_index - count) % self.hist_depth if self.step_index else 0
+        first, count = int(first), int(count)
+        fid = nat.FIELD[name]
+        names = ("sum", "count", "cells")
+        want = tuple(out) if out is not None else ((want,) if isinstance(want, str) else tuple(want))
+        if not want or any(w not in names for w in want):
+            raise ValueError(f"coarse_series: want some of {names}, not {want!r}")
+        g = nat.TfgForcingGrid(gny, gnx, 0, 0, float(grid.y0), float(grid.x0), float(grid.sy), float(grid.sx), self.row0)
+        nodes = max(gny, 0) * max(gnx, 0)
+        if out is not None:
+            import torch
+
+            kinds = {"sum": torch.float64, "count": torch.int64, "cells": torch.int64}
+            for w, t in out.items():
+                numel = (max(count, 0) if w != "cells" else 1) * nodes
+                if not (getattr(t, "is_cuda", False) and t.is_contiguous() and t.dtype == kinds[w]
+                        and t.numel() == numel and t.device.index == self.device):
+                    raise ValueError(f"out[{w!r}]: need a contiguous {kinds[w]} CUDA tensor of {numel} elements "
+                                     f"on cuda:{self.device}")
+            torch.cuda.current_stream(self.torch_device).synchronize()  # `out` may still be in use on torch's stream
+            ptr = {w: ctypes.c_void_p(out[w].data_ptr()) if w in out else None for w in names}
+            self._chk(self.lib.tfg_coarse_series(self.h, fid, first, count, ctypes.byref(g), float(threshold), ptr["sum"],
+                                                 ptr["count"], ptr["cells"], 1))
+            return out
+        shapes = {"sum": (max(count, 1), max(gny, 1), max(gnx, 1)), "count": (max(count, 1), max(gny, 1), max(gnx, 1)),
+                  "cells": (max(gny, 1), max(gnx, 1))}
+        res = {w: np.empty(shapes[w], dtype=np.float64 if w == "sum" else np.int64) for w in want}
+        ptr = {w: res[w].ctypes.data_as(ctypes.c_void_p) if w in res else None for w in names}
+        self._chk(self.lib.tfg_coarse_series(self.h, fid, first, count, ctypes.byref(g), float(threshold), ptr["sum"],
+                                             ptr["count"], ptr["cells"], 0))
+        return res
+
     def hypsometry(self, edges) -> np.ndarray:
         """[n_catch][n_bands] int64 cells of each catchment and elevation band
         of this shard (band_series's "cells" alone: no plane is read), cached

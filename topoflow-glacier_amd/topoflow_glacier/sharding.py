@@ -99,6 +99,18 @@ def allreduce_band_series(sum=None, count=None, cells=None, group=None, device=N
     return (s, *ints)
 
 
+def allreduce_coarse_series(sum=None, count=None, cells=None, group=None, device=None) -> tuple:
+    """Combine per-shard coarse series (GlacierEngine.coarse_series: per-node
+    sums, counts above the threshold, cells per node).  Row-block shards that
+    share a node row each hold a partial of that row's nodes, and a node
+    outside a shard's rows reads 0 there, so the whole grid's arrays are the
+    shards' sums: allreduce_band_series's two all-reduces (float64 sums; int64
+    counts and cells together, exact past 2^53); copies when no process group
+    is up.  None stays None.  A node's mean or covered fraction over shards
+    comes from the reduced arrays, never from the shards' own."""
+    return allreduce_band_series(sum, count, cells, group=group, device=device)
+
+
 def allreduce_catchment_elevation(sum, cells, group=None, device=None) -> np.ndarray:
     """The global reference elevation z_ref [n_catch] of
     GlacierEngine.set_catchment_forcing from the shards' per-catchment
