@@ -90,8 +90,8 @@
 // partials: fp64 sums [NB][K] in one buffer, int32 counts [NB][K] and cells [K]
 // in another (a workgroup sees fewer than 2^31 cells).  k_series_reduce folds
 // the sums over the workgroups in its fixed order; k_band_reduce_int folds the
-// integers into int64 likewise.  Both buffers are members of the handle,
-// reserved on first use and freed by tfg_destroy; band_blocks() caps the
+// integers into int64 likewise.  Both buffers are the history readers' shared
+// scratch, reserved by each call for its own K; band_blocks() caps the
 // workgroups at kSeriesMaxBlocks and so that both together stay at or under
 // kSeriesScratchMax (64 MiB): a row is K * (12 * NB + 4) bytes.
 //

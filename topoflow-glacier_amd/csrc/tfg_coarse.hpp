@@ -77,8 +77,8 @@
 // again in the unused positions and stores nothing for them) or where the
 // output lives.
 //
-// Scratch the handle keeps (allocated on first use, freed by tfg_destroy),
-// none of it depending on nslots:
+// What a call needs of the handle (the tables a cache of their own, the rest
+// the history readers' shared scratch), none of it depending on nslots:
 //   tables    (nx + nseg + 1 + 3 gny + 3 gnx) * 4 B
 //   partials  kCoarseBatch * nseg * P * (8 + 4) B, with
 //             nseg <= min(ny, gny + ny / kCoarseSegRows) and

@@ -25,7 +25,8 @@
 // policies, Event, Stream, StageRing, MappedBlock), so tfg_destroy is `delete`.
 // One definition each: by_type / by_types (the float | double instance of a
 // launch), read_flag and note_written (finite-data tracking), wait_flags,
-// step_args, kBmiToPlane.  Then the C ABI, in include/tfg.h's order.
+// step_args, kBmiToPlane; for the history readers hist_window (the checked slots,
+// in batches) and one scratch (reserve_idle).  Then the C ABI, in include/tfg.h's order.
 #include <hip/hip_runtime.h>
 #include <mutex>
 
@@ -729,21 +730,14 @@ struct tfg_handle {
   Dev<void> hist;
   Dev<double> diag;              // [n_catch][6]
   Dev<double> slab;              // [max_blocks][n_catch][6]
-  // tfg_catchment_series, allocated on first use: the workgroups' partial sums and a host call's result
-  Dev<double> series_part;       // [series_blocks][kSeriesBatch][n_catch]
-  Dev<double> series_out;        // [hist_depth][n_catch]
-  // tfg_band_series, allocated on first use: the workgroups' partials and a host call's results
-  Dev<double> band_part_sum;     // [band_blocks][band_batch][n_catch * n_bands]
-  Dev<int32_t> band_part_int;    // [band_blocks][band_batch * K + K]: counts, then cells
-  Dev<double> band_out_sum;      // [hist_depth][K]
-  Dev<int64_t> band_out_int;     // [hist_depth][K] counts, then [K] cells
-  // tfg_coarse_series, allocated on first use: the tables of the last grid (coarse_plan, kept while the
-  // grid's bytes stay the same), the workgroups' partials and a host call's copy of one batch
+  // The history readers' scratch (tfg_catchment_series, tfg_band_series, tfg_coarse_series): one reader runs
+  // at a time, on `stream`, so they share it; each call reserves what it needs (reserve_idle)
+  Dev<double> rd_part_sum;       // the workgroups' fp64 partials
+  Dev<int32_t> rd_part_int;      // their int32 partials (counts; the band series' cells after them)
+  Dev<double> rd_out_sum;        // a host call's fp64 result on the device
+  Dev<int64_t> rd_out_int;       // its int64 results (counts, then cells)
+  // tfg_coarse_series: the tables of the last grid (coarse_plan), kept while the grid's bytes stay the same
   Dev<int32_t> coarse_tab;
-  Dev<double> coarse_part_sum;   // [nseg][kCoarseBatch][P]
-  Dev<int32_t> coarse_part_cnt;  // [nseg][kCoarseBatch][P]
-  Dev<double> coarse_out_sum;    // [kCoarseBatch][gny * gnx]
-  Dev<int64_t> coarse_out_int;   // [kCoarseBatch][gny * gnx] counts, then [gny * gnx] cells
   tfg_forcing_grid coarse_grid{};  // the grid coarse_tab holds (method and pad zeroed), while coarse_valid
   CoarsePlan coarse;
   bool coarse_valid = false;
@@ -841,6 +835,15 @@ int reserve_zeroed(tfg_handle* h, B& b, size_t bytes) {
   return TFG_OK;
 }
 int ensure_qc(tfg_handle* h) { return reserve_zeroed(h, h->qc, (size_t)h->n_pad * h->rsz); }
+
+// At least `bytes` of a buffer that work queued on the handle's stream may still use (tfg_hostbuf.hpp's rule):
+// growing releases the old allocation, so the stream is drained first; nothing else waits.
+template <class B>
+hipError_t reserve_idle(tfg_handle* h, B& b, size_t bytes) {
+  if (bytes <= b.cap) return hipSuccess;
+  const hipError_t e = b.ptr ? hipStreamSynchronize(h->stream) : hipSuccess;
+  return e != hipSuccess ? e : (hipError_t)b.reserve(bytes);
+}
 
 // Split launches (include/tfg.h tfg_set_split).  The parts are whole 256-cell
 // chunks; AUTO splits grids of one to 64 rounds of the resident workgroups.
@@ -1125,6 +1128,27 @@ void* field_ptr(tfg_handle* h, int field, int index, int* dtype) {
 
 bool is_frame_field(int f) { return f == TFG_IN_P || f == TFG_IN_T_AIR || f == TFG_IN_HUM_SP || f == TFG_IN_P_AIR || f == TFG_IN_UZ; }
 bool is_hist_field(int f) { return f == TFG_OUT_H_SNOW || f == TFG_OUT_SM || f == TFG_OUT_H_ICE || f == TFG_OUT_IM || f == TFG_OUT_M_TOTAL || f == TFG_OUT_RH; }
+
+// What a reader of the output history is given: `nslots` slots of one field from slot `hist0`, following the ring.
+struct HistWindow {
+  const void* plane = nullptr;  // slot 0's plane of the field, engine type
+  int64_t stride = 0;           // elements from a slot's plane to the next slot's
+  int depth = 0, hist0 = 0, nslots = 0;
+  // for (int j0 = 0; j0 < w.nslots; j0 += B): the batch of at most B slots from the window's slot j0, which is the
+  // ring's slot slot0.
+  struct Batch { int nb, slot0; };
+  Batch batch(int j0, int B) const { return {std::min(B, nslots - j0), (hist0 + j0) % depth}; }
+};
+// The window of a call's arguments, or TFG_ERR_ARG under the caller's name.
+int hist_window(tfg_handle* h, const char* who, int field, int hist0, int nslots, HistWindow* w) {
+  auto bad = [&](const std::string& what) { return fail(h, TFG_ERR_ARG, std::string(who) + ": " + what); };
+  if (!is_hist_field(field)) return bad("field " + std::to_string(field) + " is not a history field (h_snow, SM, h_ice, IM, M_total, RH)");
+  if (hist0 < 0 || hist0 >= h->hist_depth) return bad("first history slot out of range");
+  if (nslots < 1 || nslots > h->hist_depth) return bad("slot count outside 1..hist_depth");
+  int fdt = 0;
+  *w = {field_ptr(h, field, 0, &fdt), (int64_t)kNumHist * h->n_pad, h->hist_depth, hist0, nslots};
+  return TFG_OK;
+}
 
 // tfg_update's single-step launch (KArgs::io_*); empty for every other launch
 struct IoArgs {
@@ -1873,36 +1897,30 @@ int tfg_catchment_series(tfg_handle* h, int field, int hist0, int nslots, double
   if (int rc_ = api_sync(h)) return rc_;  // after a split launch's second part
   if (!h) return fail(nullptr, TFG_ERR_ARG, "null handle");
   if (!out) return fail(h, TFG_ERR_ARG, "null out");
-  if (!is_hist_field(field))
-    return fail(h, TFG_ERR_ARG, "catchment series: field " + std::to_string(field) +
-                                    " is not a history field (h_snow, SM, h_ice, IM, M_total, RH)");
-  if (hist0 < 0 || hist0 >= h->hist_depth) return fail(h, TFG_ERR_ARG, "catchment series: first history slot out of range");
-  if (nslots < 1 || nslots > h->hist_depth) return fail(h, TFG_ERR_ARG, "catchment series: slot count outside 1..hist_depth");
+  HistWindow w;
+  if (int rc = hist_window(h, "catchment series", field, hist0, nslots, &w)) return rc;
   HIPCHK(h, hipSetDevice(h->device));
   const int blocks = series_blocks(h->n, h->n_catch);
   const int row_len = kSeriesBatch * h->n_catch;
-  HIPCHK(h, h->series_part.reserve((size_t)blocks * row_len * 8));
-  if (!out_on_device) HIPCHK(h, h->series_out.reserve((size_t)h->hist_depth * h->n_catch * 8));
-  double* dout = out_on_device ? out : h->series_out;
-  int fdt = 0;
-  const void* plane = field_ptr(h, field, 0, &fdt);  // slot 0's plane of the field, engine type
-  const int64_t stride = (int64_t)kNumHist * h->n_pad;
+  // partials [blocks][kSeriesBatch][n_catch]; a host call's result [hist_depth][n_catch]
+  HIPCHK(h, reserve_idle(h, h->rd_part_sum, (size_t)blocks * row_len * 8));
+  if (!out_on_device) HIPCHK(h, reserve_idle(h, h->rd_out_sum, (size_t)h->hist_depth * h->n_catch * 8));
+  double* dout = out_on_device ? out : h->rd_out_sum;
   const size_t lds = (size_t)row_len * 8;
-  for (int j0 = 0; j0 < nslots; j0 += kSeriesBatch) {
-    const int nb = std::min(kSeriesBatch, nslots - j0);
-    const int slot0 = (hist0 + j0) % h->hist_depth;
+  for (int j0 = 0; j0 < w.nslots; j0 += kSeriesBatch) {
+    const auto b = w.batch(j0, kSeriesBatch);
     by_type(h->engine, [&](auto t) {
       using R = typename decltype(t)::type;
       auto launch = [&](auto kern) {
-        hipLaunchKernelGGL(kern, blocks, kBlock, lds, h->stream, (const R*)plane, stride, h->hist_depth, slot0, nb,
-                           h->catch_id, h->n, h->n_catch, h->series_part);
+        hipLaunchKernelGGL(kern, blocks, kBlock, lds, h->stream, (const R*)w.plane, w.stride, w.depth, b.slot0, b.nb,
+                           h->catch_id, h->n, h->n_catch, h->rd_part_sum);
       };
       if (h->catch_id) launch(k_catch_series<R, true>);
       else launch(k_catch_series<R, false>);
     });
     HIPCHK(h, hipGetLastError());
-    const int nent = nb * h->n_catch;
-    hipLaunchKernelGGL(k_series_reduce, (nent + 15) / 16, kBlock, 0, h->stream, h->series_part, blocks, row_len, nent,
+    const int nent = b.nb * h->n_catch;
+    hipLaunchKernelGGL(k_series_reduce, (nent + 15) / 16, kBlock, 0, h->stream, h->rd_part_sum, blocks, row_len, nent,
                        dout + (int64_t)j0 * h->n_catch);
     HIPCHK(h, hipGetLastError());
   }
@@ -1929,41 +1947,35 @@ int tfg_band_series(tfg_handle* h, int field, int hist0, int nslots, const tfg_b
     if (k && !(edges.e[k] > edges.e[k - 1])) return fail(h, TFG_ERR_ARG, "band series: edges must be strictly ascending");
   }
   if (count && b->threshold != b->threshold) return fail(h, TFG_ERR_ARG, "band series: NaN threshold");
-  if (!is_hist_field(field))
-    return fail(h, TFG_ERR_ARG, "band series: field " + std::to_string(field) +
-                                    " is not a history field (h_snow, SM, h_ice, IM, M_total, RH)");
-  if (hist0 < 0 || hist0 >= h->hist_depth) return fail(h, TFG_ERR_ARG, "band series: first history slot out of range");
-  if (nslots < 1 || nslots > h->hist_depth) return fail(h, TFG_ERR_ARG, "band series: slot count outside 1..hist_depth");
+  HistWindow w;
+  if (int rc = hist_window(h, "band series", field, hist0, nslots, &w)) return rc;
   HIPCHK(h, hipSetDevice(h->device));
   const int K = h->n_catch * b->n_bands;
   const bool planes = sum || count;               // without them one cells-only launch, no plane read
   const int NB = planes ? band_batch(K) : 0;
   const int blocks = band_blocks(h->n, K);
   const int row_sum = NB * K, row_int = NB * K + K;
-  if (sum) HIPCHK(h, h->band_part_sum.reserve((size_t)blocks * row_sum * 8));
-  HIPCHK(h, h->band_part_int.reserve((size_t)blocks * (band_batch(K) * K + K) * 4));
+  // partials [blocks][NB][K] sums, [blocks][NB * K + K] counts then cells; a host call's [hist_depth][K] sums, [hist_depth][K] counts then [K] cells
+  if (sum) HIPCHK(h, reserve_idle(h, h->rd_part_sum, (size_t)blocks * row_sum * 8));
+  HIPCHK(h, reserve_idle(h, h->rd_part_int, (size_t)blocks * (band_batch(K) * K + K) * 4));
   if (!out_on_device) {
-    if (sum) HIPCHK(h, h->band_out_sum.reserve((size_t)h->hist_depth * K * 8));
-    HIPCHK(h, h->band_out_int.reserve(((size_t)h->hist_depth * K + K) * 8));
+    if (sum) HIPCHK(h, reserve_idle(h, h->rd_out_sum, (size_t)h->hist_depth * K * 8));
+    HIPCHK(h, reserve_idle(h, h->rd_out_int, ((size_t)h->hist_depth * K + K) * 8));
   }
-  double* dsum = out_on_device ? sum : (double*)h->band_out_sum;
-  int64_t* dcount = out_on_device ? count : (int64_t*)h->band_out_int;
-  int64_t* dcells = out_on_device ? cells : (int64_t*)h->band_out_int + (int64_t)h->hist_depth * K;
-  int fdt = 0;
-  const void* plane = field_ptr(h, field, 0, &fdt);  // slot 0's plane of the field, engine type
-  const int64_t stride = (int64_t)kNumHist * h->n_pad;
+  double* dsum = out_on_device ? sum : (double*)h->rd_out_sum;
+  int64_t* dcount = out_on_device ? count : (int64_t*)h->rd_out_int;
+  int64_t* dcells = out_on_device ? cells : (int64_t*)h->rd_out_int + (int64_t)h->hist_depth * K;
   const size_t lds = band_lds_bytes(NB, K);
   const int step = planes ? NB : nslots;  // the cells-only call: one trip
   for (int j0 = 0; j0 < nslots; j0 += step) {
-    const int nb = planes ? std::min(NB, nslots - j0) : 1;
-    const int slot0 = (hist0 + j0) % h->hist_depth;
+    const int nb = planes ? w.batch(j0, step).nb : 1, slot0 = w.batch(j0, step).slot0;
     const int what = (sum ? kBandSum : 0) | (count ? kBandCount : 0) | (cells && j0 == 0 ? kBandCells : 0);
     by_type(h->engine, [&](auto t) {
       using R = typename decltype(t)::type;
       auto launch = [&](auto kern) {
-        hipLaunchKernelGGL(kern, blocks, kBlock, lds, h->stream, (const R*)plane, stride, h->hist_depth, slot0, nb,
+        hipLaunchKernelGGL(kern, blocks, kBlock, lds, h->stream, (const R*)w.plane, w.stride, w.depth, slot0, nb,
                            h->catch_id, (const R*)h->stat.bytes(), edges, b->n_bands, b->threshold, what, h->n, K,
-                           h->band_part_sum, h->band_part_int);
+                           h->rd_part_sum, h->rd_part_int);
       };
       auto with_nb = [&](auto c) {
         constexpr bool C = decltype(c)::value;
@@ -1980,17 +1992,17 @@ int tfg_band_series(tfg_handle* h, int field, int hist0, int nslots, const tfg_b
     HIPCHK(h, hipGetLastError());
     const int nent = nb * K;
     if (sum) {
-      hipLaunchKernelGGL(k_series_reduce, (nent + 15) / 16, kBlock, 0, h->stream, h->band_part_sum, blocks, row_sum, nent,
+      hipLaunchKernelGGL(k_series_reduce, (nent + 15) / 16, kBlock, 0, h->stream, h->rd_part_sum, blocks, row_sum, nent,
                          dsum + (int64_t)j0 * K);
       HIPCHK(h, hipGetLastError());
     }
     if (count) {
-      hipLaunchKernelGGL(k_band_reduce_int, (nent + 15) / 16, kBlock, 0, h->stream, h->band_part_int, blocks, row_int, nent,
+      hipLaunchKernelGGL(k_band_reduce_int, (nent + 15) / 16, kBlock, 0, h->stream, h->rd_part_int, blocks, row_int, nent,
                          dcount + (int64_t)j0 * K);
       HIPCHK(h, hipGetLastError());
     }
     if (what & kBandCells) {
-      hipLaunchKernelGGL(k_band_reduce_int, (K + 15) / 16, kBlock, 0, h->stream, h->band_part_int + row_sum, blocks, row_int,
+      hipLaunchKernelGGL(k_band_reduce_int, (K + 15) / 16, kBlock, 0, h->stream, h->rd_part_int + row_sum, blocks, row_int,
                          K, dcells);
       HIPCHK(h, hipGetLastError());
     }
@@ -2021,7 +2033,7 @@ int coarse_prepare(tfg_handle* h, const tfg_forcing_grid& g) {
   StageRing::Slot* s = nullptr;  // through the pinned ring: one queued copy, no host wait
   HIPCHK(h, h->in_ring.acquire(bytes, false, &s));
   std::memcpy(s->host.ptr, tab.data(), bytes);
-  HIPCHK(h, h->coarse_tab.reserve(bytes));
+  HIPCHK(h, reserve_idle(h, h->coarse_tab, bytes));
   HIPCHK(h, hipMemcpyAsync(h->coarse_tab.ptr, s->host.ptr, bytes, hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, StageRing::commit(*s, h->stream));
   h->coarse = p;
@@ -2065,45 +2077,40 @@ int tfg_coarse_series(tfg_handle* h, int field, int hist0, int nslots, const tfg
     return fail(h, TFG_ERR_ARG, "coarse series: y0, x0, sy and sx must be finite");
   if (g->row0 < 0) return fail(h, TFG_ERR_ARG, "coarse series: row0 must be >= 0");
   if (count && threshold != threshold) return fail(h, TFG_ERR_ARG, "coarse series: NaN threshold");
-  if (!is_hist_field(field))
-    return fail(h, TFG_ERR_ARG, "coarse series: field " + std::to_string(field) +
-                                    " is not a history field (h_snow, SM, h_ice, IM, M_total, RH)");
-  if (hist0 < 0 || hist0 >= h->hist_depth) return fail(h, TFG_ERR_ARG, "coarse series: first history slot out of range");
-  if (nslots < 1 || nslots > h->hist_depth) return fail(h, TFG_ERR_ARG, "coarse series: slot count outside 1..hist_depth");
+  HistWindow w;  // checked for a cells-only call too
+  if (int rc = hist_window(h, "coarse series", field, hist0, nslots, &w)) return rc;
   HIPCHK(h, hipSetDevice(h->device));
   if (int rc = coarse_prepare(h, *g)) return rc;
   const CoarsePlan& p = h->coarse;
   const int32_t* tab = h->coarse_tab;
   const size_t nodes = (size_t)g->gny * (size_t)g->gnx;
   const size_t part_len = (size_t)p.nseg * kCoarseBatch * p.P;
-  if (sum) HIPCHK(h, h->coarse_part_sum.reserve(part_len * 8));
-  if (count) HIPCHK(h, h->coarse_part_cnt.reserve(part_len * 4));
+  // partials [nseg][kCoarseBatch][P] sums and counts; a host call's copy of one batch, [kCoarseBatch][nodes] each, then [nodes] cells
+  if (sum) HIPCHK(h, reserve_idle(h, h->rd_part_sum, part_len * 8));
+  if (count) HIPCHK(h, reserve_idle(h, h->rd_part_int, part_len * 4));
   if (!out_on_device) {
-    if (sum) HIPCHK(h, h->coarse_out_sum.reserve(kCoarseBatch * nodes * 8));
-    HIPCHK(h, h->coarse_out_int.reserve((kCoarseBatch * nodes + nodes) * 8));
+    if (sum) HIPCHK(h, reserve_idle(h, h->rd_out_sum, kCoarseBatch * nodes * 8));
+    HIPCHK(h, reserve_idle(h, h->rd_out_int, (kCoarseBatch * nodes + nodes) * 8));
   }
   if (cells) {  // rows(J) cols(I): no plane is read
-    int64_t* dcells = out_on_device ? cells : (int64_t*)h->coarse_out_int + kCoarseBatch * nodes;
+    int64_t* dcells = out_on_device ? cells : (int64_t*)h->rd_out_int + kCoarseBatch * nodes;
     hipLaunchKernelGGL(k_coarse_cells, (int)std::min<size_t>((nodes + kBlock - 1) / kBlock, 4096), kBlock, 0, h->stream,
                        tab + p.o_rows, tab + p.o_cols, g->gny, g->gnx, dcells);
     HIPCHK(h, hipGetLastError());
     if (!out_on_device) HIPCHK(h, hipMemcpyAsync(cells, dcells, nodes * 8, hipMemcpyDeviceToHost, h->stream));
   }
   if (sum || count) {
-    int fdt = 0;
-    const void* plane = field_ptr(h, field, 0, &fdt);  // slot 0's plane of the field, engine type
-    const int64_t stride = (int64_t)kNumHist * h->n_pad;
     const int v = 16 / (int)h->rsz;
-    const bool vec = h->nx % v == 0 && (uintptr_t)plane % 16 == 0 && (stride * (int64_t)h->rsz) % 16 == 0;
-    for (int j0 = 0; j0 < nslots; j0 += kCoarseBatch) {
-      const int nb = std::min(kCoarseBatch, nslots - j0);
-      const int slot0 = (hist0 + j0) % h->hist_depth;
+    const bool vec = h->nx % v == 0 && (uintptr_t)w.plane % 16 == 0 && (w.stride * (int64_t)h->rsz) % 16 == 0;
+    for (int j0 = 0; j0 < w.nslots; j0 += kCoarseBatch) {
+      const auto b = w.batch(j0, kCoarseBatch);
+      const int nb = b.nb;
       by_type(h->engine, [&](auto t) {
         using R = typename decltype(t)::type;
         auto launch = [&](auto kern) {
-          hipLaunchKernelGGL(kern, p.nseg * p.ntiles, kBlock, 0, h->stream, (const R*)plane, stride, h->hist_depth, slot0, nb,
+          hipLaunchKernelGGL(kern, p.nseg * p.ntiles, kBlock, 0, h->stream, (const R*)w.plane, w.stride, w.depth, b.slot0, nb,
                              (int)h->nx, tab + p.o_seg, tab + p.o_pcol, p.ntiles, p.P, threshold,
-                             (double*)h->coarse_part_sum, (int32_t*)h->coarse_part_cnt);
+                             (double*)h->rd_part_sum, (int32_t*)h->rd_part_int);
         };
         auto with_what = [&](auto vc) {
           constexpr bool VEC = decltype(vc)::value;
@@ -2117,14 +2124,14 @@ int tfg_coarse_series(tfg_handle* h, int field, int hist0, int nslots, const tfg
       HIPCHK(h, hipGetLastError());
       // a device output takes the batch's rows in place; a host output is copied out batch by batch
       if (sum) {
-        double* dsum = out_on_device ? sum + (size_t)j0 * nodes : (double*)h->coarse_out_sum;
-        if (int rc = coarse_fold(h, (const double*)h->coarse_part_sum, nb, *g, dsum)) return rc;
+        double* dsum = out_on_device ? sum + (size_t)j0 * nodes : (double*)h->rd_out_sum;
+        if (int rc = coarse_fold(h, (const double*)h->rd_part_sum, nb, *g, dsum)) return rc;
         if (!out_on_device)
           HIPCHK(h, hipMemcpyAsync(sum + (size_t)j0 * nodes, dsum, (size_t)nb * nodes * 8, hipMemcpyDeviceToHost, h->stream));
       }
       if (count) {
-        int64_t* dcount = out_on_device ? count + (size_t)j0 * nodes : (int64_t*)h->coarse_out_int;
-        if (int rc = coarse_fold(h, (const int32_t*)h->coarse_part_cnt, nb, *g, dcount)) return rc;
+        int64_t* dcount = out_on_device ? count + (size_t)j0 * nodes : (int64_t*)h->rd_out_int;
+        if (int rc = coarse_fold(h, (const int32_t*)h->rd_part_int, nb, *g, dcount)) return rc;
         if (!out_on_device)
           HIPCHK(h, hipMemcpyAsync(count + (size_t)j0 * nodes, dcount, (size_t)nb * nodes * 8, hipMemcpyDeviceToHost, h->stream));
       }
@@ -2139,23 +2146,17 @@ int tfg_cell_aggregate(tfg_handle* h, int field, int hist0, int nslots, const tf
   if (!h) return fail(nullptr, TFG_ERR_ARG, "null handle");
   if (!acc) return fail(h, TFG_ERR_ARG, "cell aggregate: null acc");
   if (!acc->sum && !acc->vmax && !acc->vmin && !acc->count) return fail(h, TFG_ERR_ARG, "cell aggregate: no statistic requested");
-  if (!is_hist_field(field))
-    return fail(h, TFG_ERR_ARG, "cell aggregate: field " + std::to_string(field) +
-                                    " is not a history field (h_snow, SM, h_ice, IM, M_total, RH)");
-  if (hist0 < 0 || hist0 >= h->hist_depth) return fail(h, TFG_ERR_ARG, "cell aggregate: first history slot out of range");
-  if (nslots < 1 || nslots > h->hist_depth) return fail(h, TFG_ERR_ARG, "cell aggregate: slot count outside 1..hist_depth");
+  HistWindow w;
+  if (int rc = hist_window(h, "cell aggregate", field, hist0, nslots, &w)) return rc;
   if (acc->count && acc->threshold != acc->threshold) return fail(h, TFG_ERR_ARG, "cell aggregate: NaN threshold");
   HIPCHK(h, hipSetDevice(h->device));
-  int fdt = 0;
-  const void* plane = field_ptr(h, field, 0, &fdt);  // slot 0's plane of the field, engine type
-  const int64_t stride = (int64_t)kNumHist * h->n_pad;
   auto aligned = [](const void* p, int bit) { return p && ((uintptr_t)p & 15) == 0 ? bit : 0; };
   const int vec = aligned(acc->sum, kAggVecSum) | aligned(acc->vmax, kAggVecMax) | aligned(acc->vmin, kAggVecMin) |
                   aligned(acc->count, kAggVecCount);
   by_type(h->engine, [&](auto t) {
     using R = typename decltype(t)::type;
     hipLaunchKernelGGL(k_cell_aggregate<R>, aggregate_blocks(h->n, 16 / (int)sizeof(R)), kBlock, 0, h->stream,
-                       (const R*)plane, stride, h->hist_depth, hist0, nslots, h->n, acc->sum, (R*)acc->vmax, (R*)acc->vmin,
+                       (const R*)w.plane, w.stride, w.depth, hist0, nslots, h->n, acc->sum, (R*)acc->vmax, (R*)acc->vmin,
                        acc->count, acc->threshold, init != 0 ? 1 : 0, vec);
   });
   HIPCHK(h, hipGetLastError());

@@ -43,8 +43,8 @@
 // NaN reaches exactly the (slot, catchment) entry of its cell: other ids'
 // passes and other slots see a selected 0, never a product.
 //
-// Scratch: partials [workgroups][kSeriesBatch][n_catch] fp64, allocated on the
-// first call and freed by tfg_destroy.  series_blocks() caps the workgroups at
+// Scratch: partials [workgroups][kSeriesBatch][n_catch] fp64, in the scratch
+// the history readers share.  series_blocks() caps the workgroups at
 // kSeriesMaxBlocks and at kSeriesScratchMax / (kSeriesBatch * n_catch * 8), and
 // a call loops over batches of kSeriesBatch slots, so the scratch stays at or
 // under 64 MiB whatever the arguments: 4096 rows of 64 B * n_catch up to 256

@@ -3,8 +3,8 @@ monthly or seasonal melt and runoff depth, mean and peak snow depth, hours
 with melt, snow-cover duration.
 
 The planes of the last ``hist_depth`` steps are resident in the engine's
-history, so the model advances in blocks of at most ``hist_depth`` steps (the
-blocking of hydrograph.catchment_hydrographs) and each block's slots are
+history, so the model advances in blocks of at most ``hist_depth`` steps
+(blocks.run_blocks) and each block's slots are
 folded on the device into per-cell accumulators
 (GlacierEngine.cell_aggregate, tfg_cell_aggregate), cut where a period of
 ``every`` steps ends.  No plane crosses to the host and no host wait separates
@@ -16,6 +16,8 @@ shard's maps are its rows of the whole grid's.
 from __future__ import annotations
 
 import numpy as np
+
+from .blocks import check_steps, run_blocks
 
 __all__ = ["STATS", "PeriodFolder", "aggregated_run"]
 
@@ -140,19 +142,9 @@ def aggregated_run(eng, nsteps: int, every: int, fields, frames=None, on_block=N
     Returns ``{"periods": [nperiods] steps of each period (the last may be
     short)}`` and, without on_period, ``"stats": {field: {statistic:
     [nperiods][ny][nx] host array}}``."""
-    nsteps = int(nsteps)
-    if nsteps < 1:
-        raise ValueError("nsteps must be >= 1")
-    if frames is not None and len(frames) != nsteps:
-        raise ValueError("one forcing frame index per step")
+    nsteps = check_steps(nsteps, frames)
     folder = PeriodFolder(eng, every, fields, on_period=on_period)
-    depth = int(eng.hist_depth)
-    for k0 in range(0, nsteps, depth):
-        k1 = min(k0 + depth, nsteps)
-        if on_block is not None:
-            on_block(k0, k1)
-        first = eng.step_index % depth  # the slot the block's first step writes
-        eng.run(k1 - k0, frames=None if frames is None else frames[k0:k1])
+    for k0, k1, first in run_blocks(eng, nsteps, frames, on_block):
         folder.fold(first, k1 - k0)
     folder.finish()
     eng.sync()

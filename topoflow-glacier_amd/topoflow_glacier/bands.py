@@ -4,17 +4,21 @@ hypsometry and the snow line, per catchment and per period of steps.
 
 A glacier model is read mostly as a function of elevation.  The planes of the
 last ``hist_depth`` steps are resident in the engine's history, so the model
-advances in blocks of at most ``hist_depth`` steps (the blocking of
-hydrograph.catchment_hydrographs and aggregate.aggregated_run) and each
-block's planes are reduced on the device per catchment and elevation band
+advances in blocks of at most ``hist_depth`` steps (blocks.run_blocks) and
+each block's planes are reduced on the device per catchment and elevation band
 (GlacierEngine.band_series, tfg_band_series).  What comes back per block is
 [steps][n_catch][n_bands]: small, so the periods are accumulated on the host
-in step order, and row-block shards are combined in one all-reduce at the end.
+in step order, and row-block shards are combined in one all-reduce at the end
+(blocks.period_run).
 """
 
 from __future__ import annotations
 
+import functools
+
 import numpy as np
+
+from .blocks import period_run
 
 __all__ = ["band_edges", "banded_run", "snow_line"]
 
@@ -32,11 +36,6 @@ def band_edges(z_min: float, z_max: float, width: float) -> np.ndarray:
     if n > 64:
         raise ValueError(f"band_edges: {n} bands; tfg_band_series takes at most 64")
     return z_min + width * np.arange(n + 1, dtype=np.float64)
-
-
-def _per_cell(x, cells):
-    """x / cells over the last two axes, 0 where a band has no cells."""
-    return np.where(cells > 0, x / np.maximum(cells, 1), 0.0)
 
 
 def banded_run(eng, nsteps: int, every: int, edges, fields, frames=None, threshold=0.0, group=None) -> dict:
@@ -61,47 +60,14 @@ def banded_run(eng, nsteps: int, every: int, edges, fields, frames=None, thresho
     fraction = count / (steps * cells).  A band without cells reads 0 in all
     four.  When both "SM" and "IM" are among the fields, also ``"melt_depth"``
     = (sum SM + sum IM) * dt * 3600 / cells [m per period]."""
-    nsteps, every = int(nsteps), int(every)
-    if nsteps < 1 or every < 1:
-        raise ValueError("nsteps and every must be >= 1")
-    if frames is not None and len(frames) != nsteps:
-        raise ValueError("one forcing frame index per step")
-    fields = (fields,) if isinstance(fields, str) else tuple(fields)
-    if not fields:
-        raise ValueError("banded_run: no field requested")
-    thr = {f: float(threshold.get(f, 0.0)) if isinstance(threshold, dict) else float(threshold) for f in fields}
-    edges = np.asarray(edges, dtype=np.float64).reshape(-1)
-    nper = -(-nsteps // every)
-    lengths = np.minimum(every, nsteps - every * np.arange(nper)).astype(np.int64)
-    shape = (nper, int(eng.n_catch), edges.size - 1)
-    sums = {f: np.zeros(shape, dtype=np.float64) for f in fields}
-    counts = {f: np.zeros(shape, dtype=np.int64) for f in fields}
-    cells = None
-    depth = int(eng.hist_depth)
-    for k0 in range(0, nsteps, depth):
-        k1 = min(k0 + depth, nsteps)
-        first = eng.step_index % depth  # the slot the block's first step writes
-        eng.run(k1 - k0, frames=None if frames is None else frames[k0:k1])
-        for f in fields:
-            want = ("sum", "count", "cells") if cells is None else ("sum", "count")
-            r = eng.band_series(f, edges, first=first, count=k1 - k0, threshold=thr[f], want=want)
-            if cells is None:
-                cells = r["cells"]
-            for j in range(k1 - k0):  # step order: a period's sum is a left fold over its steps
-                sums[f][(k0 + j) // every] += r["sum"][j]
-                counts[f][(k0 + j) // every] += r["count"][j]
-    from .sharding import allreduce_band_series
+    def reader():  # after period_run's checks, where the edges were always parsed
+        from .sharding import allreduce_band_series
 
-    s_all, c_all, cells = allreduce_band_series(np.stack([sums[f] for f in fields]), np.stack([counts[f] for f in fields]),
-                                                cells, group=group)
-    res = {"periods": lengths, "edges": edges, "cells": cells, "fields": {}}
-    slots = lengths[:, None, None]
-    for i, f in enumerate(fields):
-        res["fields"][f] = {"sum": s_all[i], "count": c_all[i], "mean": _per_cell(s_all[i], cells),
-                            "fraction": _per_cell(c_all[i] / slots, cells)}
-    if "SM" in fields and "IM" in fields:
-        melt = res["fields"]["SM"]["sum"] + res["fields"]["IM"]["sum"]
-        res["melt_depth"] = _per_cell(melt * (float(eng.params.dt) * 3600.0), cells)
+        res["edges"] = e = np.asarray(edges, dtype=np.float64).reshape(-1)
+        return functools.partial(eng.band_series, edges=e), (int(eng.n_catch), e.size - 1), allreduce_band_series
+
+    res = {}
+    res.update(period_run(eng, "banded_run", nsteps, every, fields, reader, frames=frames, threshold=threshold, group=group))
     return res
 
 

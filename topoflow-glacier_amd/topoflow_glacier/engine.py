@@ -11,7 +11,6 @@ All arithmetic happens in the HIP kernels; this class never computes physics.
 
 from __future__ import annotations
 
-import builtins
 import ctypes
 import os
 
@@ -20,7 +19,7 @@ import numpy as np
 from . import _native as nat
 from .physics.clock import StepClock
 
-__all__ = ["GlacierEngine", "UpdateBatch", "params_from_config", "update_many"]
+__all__ = ["GlacierEngine", "UpdateBatch", "params_from_config", "ring_window", "update_many"]
 
 _ENGINES = {"float32": nat.F32, "float64": nat.F64}
 _NP = {nat.F32: np.float32, nat.F64: np.float64}
@@ -41,6 +40,19 @@ def params_from_config(cfg) -> nat.TfgParams:
     p.satterlund = int(bool(cfg.SATTERLUND))
     p.ring_len = int(3 * np.float64(24) / cfg.dt)  # :296
     return p
+
+
+def ring_window(step_index: int, hist_depth: int, first=None, count=None) -> tuple:
+    """(first, count) of a history reader's window after step_index steps on
+    a ring of hist_depth slots: by default the slots of the last
+    min(step_index, hist_depth) steps in step order (one slot, slot 0, before
+    the first step).  A given value is passed on as an int whatever it is:
+    the library rejects a slot or a count out of range."""
+    if count is None:
+        count = max(min(step_index, hist_depth), 1)
+    if first is None:
+        first = (step_index - count) % hist_depth if step_index else 0
+    return int(first), int(count)
 
 
 class GlacierEngine:
@@ -673,6 +685,52 @@ class GlacierEngine:
             self._catch_cells = cells
         return self._catch_cells
 
+    # -- readers of the output history ----------------------------------------------
+    def _take_device_out(self, outs=()) -> int:
+        """The readers' one check of device outputs (tensor, dtype, element count)
+        and one drain of torch's stream.  The index of the first that is not a
+        contiguous CUDA tensor of that dtype and count on the engine's device, for
+        the caller to raise under its name; else -1 after waiting for torch's
+        current stream, where a tensor handed to the engine's may still be in use."""
+        import torch
+
+        dev = self.device
+        for i, (t, dtype, numel) in enumerate(outs):
+            if not (getattr(t, "is_cuda", False) and t.is_contiguous() and t.dtype == dtype and t.numel() == numel
+                    and t.device.index == dev):
+                return i
+        torch.cuda.current_stream(dev).synchronize()
+        return -1
+
+    def _keyed_outputs(self, who: str, tail, count: int, want, out) -> tuple:
+        """What band_series and coarse_series hand to their library call: (res,
+        [sum, count, cells pointers, None where not wanted], on_device) for sums and
+        counts [count][*tail] and cells [*tail]; a given `out` is res.  An axis or a
+        count of 0 or below still reaches the library, which rejects it: host arrays
+        take 1 for it, a device `out` 0 elements."""
+        names = ("sum", "count", "cells")
+        want = tuple(out) if out is not None else ((want,) if isinstance(want, str) else tuple(want))
+        bad = not want
+        for w in want:
+            bad = bad or w not in names
+        if bad:
+            raise ValueError(f"{who}: want some of {names}, not {want!r}")
+        if out is not None:
+            import torch
+
+            per_slot = max(tail[0], 0) * max(tail[1], 0)
+            outs = [(t, torch.float64 if w == "sum" else torch.int64, per_slot if w == "cells" else max(count, 0) * per_slot)
+                    for w, t in out.items()]
+            i = self._take_device_out(outs)
+            if i >= 0:
+                raise ValueError(f"out[{want[i]!r}]: need a contiguous {outs[i][1]} CUDA tensor of {outs[i][2]} elements "
+                                 f"on cuda:{self.device}")
+            return out, [ctypes.c_void_p(out[w].data_ptr()) if w in out else None for w in names], 1
+        per_key = (max(tail[0], 1), max(tail[1], 1))
+        res = {w: np.empty(per_key if w == "cells" else (max(count, 1), *per_key),
+                           dtype=np.float64 if w == "sum" else np.int64) for w in want}
+        return res, [res[w].ctypes.data_as(ctypes.c_void_p) if w in res else None for w in names], 0
+
     def catchment_series(self, name: str = "M_total", first: int | None = None, count: int | None = None,
                          reduce: str = "sum", out=None):
         """[count][n_catch] float64: per catchment, the sum (or, reduce="mean",
@@ -691,22 +749,16 @@ class GlacierEngine:
         sync()s (or orders its stream after the engine's) before reading."""
         if reduce not in ("sum", "mean"):
             raise ValueError(f"reduce must be 'sum' or 'mean', not {reduce!r}")
-        if count is None:
-            count = max(min(self.step_index, self.hist_depth), 1)
-        if first is None:
-            first = (self.step_index - count) % self.hist_depth if self.step_index else 0
-        first, count = int(first), int(count)
+        first, count = ring_window(self.step_index, self.hist_depth, first, count)
         fid = nat.FIELD[name]
         if out is not None:
             import torch
 
             if reduce != "sum":
                 raise ValueError("a device `out` takes sums only")
-            if not (getattr(out, "is_cuda", False) and out.is_contiguous() and out.dtype == torch.float64
-                    and out.numel() == max(count, 0) * self.n_catch and out.device.index == self.device):
+            if self._take_device_out(((out, torch.float64, max(count, 0) * self.n_catch),)) >= 0:
                 raise ValueError(f"out: need a contiguous float64 CUDA tensor of {count} x {self.n_catch} elements "
                                  f"on cuda:{self.device}")
-            torch.cuda.current_stream(out.device).synchronize()  # `out` may still be in use on torch's stream
             self._chk(self.lib.tfg_catchment_series(self.h, fid, first, count, ctypes.c_void_p(out.data_ptr()), 1))
             return out
         res = np.empty((max(count, 1), self.n_catch), dtype=np.float64)
@@ -743,38 +795,11 @@ class GlacierEngine:
         nb = e.size - 1
         if nb < 1:
             raise ValueError("band_series: need at least two edges")
-        if count is None:
-            count = max(min(self.step_index, self.hist_depth), 1)
-        if first is None:
-            first = (self.step_index - count) % self.hist_depth if self.step_index else 0
-        first, count = int(first), int(count)
+        first, count = ring_window(self.step_index, self.hist_depth, first, count)
         fid = nat.FIELD[name]
-        names = ("sum", "count", "cells")
-        want = tuple(out) if out is not None else ((want,) if isinstance(want, str) else tuple(want))
-        if not want or any(w not in names for w in want):
-            raise ValueError(f"band_series: want some of {names}, not {want!r}")
+        res, ptr, on_device = self._keyed_outputs("band_series", (self.n_catch, nb), count, want, out)
         bands = nat.TfgBands(nb, 0, e.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), float(threshold))
-        shapes = {"sum": (max(count, 1), self.n_catch, nb), "count": (max(count, 1), self.n_catch, nb),
-                  "cells": (self.n_catch, nb)}
-        if out is not None:
-            import torch
-
-            kinds = {"sum": torch.float64, "count": torch.int64, "cells": torch.int64}
-            for w, t in out.items():
-                numel = (max(count, 0) if w != "cells" else 1) * self.n_catch * nb
-                if not (getattr(t, "is_cuda", False) and t.is_contiguous() and t.dtype == kinds[w]
-                        and t.numel() == numel and t.device.index == self.device):
-                    raise ValueError(f"out[{w!r}]: need a contiguous {kinds[w]} CUDA tensor of {numel} elements "
-                                     f"on cuda:{self.device}")
-            torch.cuda.current_stream(self.torch_device).synchronize()  # `out` may still be in use on torch's stream
-            ptr = {w: ctypes.c_void_p(out[w].data_ptr()) if w in out else None for w in names}
-            self._chk(self.lib.tfg_band_series(self.h, fid, first, count, ctypes.byref(bands), ptr["sum"], ptr["count"],
-                                               ptr["cells"], 1))
-            return out
-        res = {w: np.empty(shapes[w], dtype=np.float64 if w == "sum" else np.int64) for w in want}
-        ptr = {w: res[w].ctypes.data_as(ctypes.c_void_p) if w in res else None for w in names}
-        self._chk(self.lib.tfg_band_series(self.h, fid, first, count, ctypes.byref(bands), ptr["sum"], ptr["count"],
-                                           ptr["cells"], 0))
+        self._chk(self.lib.tfg_band_series(self.h, fid, first, count, ctypes.byref(bands), *ptr, on_device))
         return res
 
     def coarse_series(self, name: str, grid, first: int | None = None, count: int | None = None,
@@ -806,39 +831,11 @@ class GlacierEngine:
         stream rule (torch's current stream is drained first; the caller
         sync()s before reading), and `out` is returned."""
         gny, gnx = int(grid.gny), int(grid.gnx)
-        if count is None:
-            count = max(min(self.step_index, self.hist_depth), 1)
-        if first is None:
-            first = (self.step_index - count) % self.hist_depth if self.step_index else 0
-        first, count = int(first), int(count)
+        first, count = ring_window(self.step_index, self.hist_depth, first, count)
         fid = nat.FIELD[name]
-        names = ("sum", "count", "cells")
-        want = tuple(out) if out is not None else ((want,) if isinstance(want, str) else tuple(want))
-        if not want or any(w not in names for w in want):
-            raise ValueError(f"coarse_series: want some of {names}, not {want!r}")
+        res, ptr, on_device = self._keyed_outputs("coarse_series", (gny, gnx), count, want, out)
         g = nat.TfgForcingGrid(gny, gnx, 0, 0, float(grid.y0), float(grid.x0), float(grid.sy), float(grid.sx), self.row0)
-        nodes = max(gny, 0) * max(gnx, 0)
-        if out is not None:
-            import torch
-
-            kinds = {"sum": torch.float64, "count": torch.int64, "cells": torch.int64}
-            for w, t in out.items():
-                numel = (max(count, 0) if w != "cells" else 1) * nodes
-                if not (getattr(t, "is_cuda", False) and t.is_contiguous() and t.dtype == kinds[w]
-                        and t.numel() == numel and t.device.index == self.device):
-                    raise ValueError(f"out[{w!r}]: need a contiguous {kinds[w]} CUDA tensor of {numel} elements "
-                                     f"on cuda:{self.device}")
-            torch.cuda.current_stream(self.torch_device).synchronize()  # `out` may still be in use on torch's stream
-            ptr = {w: ctypes.c_void_p(out[w].data_ptr()) if w in out else None for w in names}
-            self._chk(self.lib.tfg_coarse_series(self.h, fid, first, count, ctypes.byref(g), float(threshold), ptr["sum"],
-                                                 ptr["count"], ptr["cells"], 1))
-            return out
-        shapes = {"sum": (max(count, 1), max(gny, 1), max(gnx, 1)), "count": (max(count, 1), max(gny, 1), max(gnx, 1)),
-                  "cells": (max(gny, 1), max(gnx, 1))}
-        res = {w: np.empty(shapes[w], dtype=np.float64 if w == "sum" else np.int64) for w in want}
-        ptr = {w: res[w].ctypes.data_as(ctypes.c_void_p) if w in res else None for w in names}
-        self._chk(self.lib.tfg_coarse_series(self.h, fid, first, count, ctypes.byref(g), float(threshold), ptr["sum"],
-                                             ptr["count"], ptr["cells"], 0))
+        self._chk(self.lib.tfg_coarse_series(self.h, fid, first, count, ctypes.byref(g), float(threshold), *ptr, on_device))
         return res
 
     def hypsometry(self, edges) -> np.ndarray:
@@ -881,11 +878,7 @@ class GlacierEngine:
         reading."""
         import torch
 
-        if count is None:
-            count = builtins.max(builtins.min(self.step_index, self.hist_depth), 1)  # max, min: arguments here
-        if first is None:
-            first = (self.step_index - count) % self.hist_depth if self.step_index else 0
-        first, count = int(first), int(count)
+        first, count = ring_window(self.step_index, self.hist_depth, first, count)
         fid = nat.FIELD[name]
         eng_dtype = {nat.F32: torch.float32, nat.F64: torch.float64}[self.dtype_code]
         given = (("sum", sum, torch.float64), ("max", max, eng_dtype), ("min", min, eng_dtype), ("above", above, torch.int32))
@@ -905,7 +898,7 @@ class GlacierEngine:
             raise ValueError("cell_aggregate: the threshold of `above` is NaN")
         ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
         acc = nat.TfgCellStats(ptr(sum), ptr(max), ptr(min), ptr(above), threshold)
-        torch.cuda.current_stream(self.torch_device).synchronize()  # the buffers may still be in use on torch's stream
+        self._take_device_out()  # no `out` of that one form here: the drain alone
         self._chk(self.lib.tfg_cell_aggregate(self.h, fid, first, count, ctypes.byref(acc), 1 if init else 0))
 
 

@@ -6,8 +6,8 @@ The reference's driver emits, per catchment and step, the runoff
 routes it through a boxcar (:129-131).  On a grid with a catchment-id raster
 the same series is the per-catchment sum of every step's M_total plane.  The
 planes of the last ``hist_depth`` steps are resident in the engine's history,
-so the model advances in blocks of at most ``hist_depth`` steps and each
-block's planes are reduced on the device (GlacierEngine.catchment_series,
+so the model advances in blocks of at most ``hist_depth`` steps
+(blocks.run_blocks) and each block's planes are reduced on the device (GlacierEngine.catchment_series,
 tfg_catchment_series) into the block's rows of one device buffer: no plane
 crosses to the host, no host wait separates the blocks, and the buffer is
 copied out once at the end.
@@ -17,6 +17,7 @@ from __future__ import annotations
 
 import numpy as np
 
+from .blocks import check_steps, run_blocks
 from .routing import boxcar_route
 
 __all__ = ["catchment_hydrographs", "forced_catchment_hydrographs"]
@@ -42,19 +43,9 @@ def catchment_hydrographs(eng, nsteps: int, frames=None, group=None, taps: int =
     """
     import torch
 
-    nsteps = int(nsteps)
-    if nsteps < 1:
-        raise ValueError("nsteps must be >= 1")
-    if frames is not None and len(frames) != nsteps:
-        raise ValueError("one forcing frame index per step")
-    depth = int(eng.hist_depth)
+    nsteps = check_steps(nsteps, frames)
     buf = torch.empty((nsteps, int(eng.n_catch)), dtype=torch.float64, device=eng.torch_device)
-    for k0 in range(0, nsteps, depth):
-        k1 = min(k0 + depth, nsteps)
-        if on_block is not None:
-            on_block(k0, k1)
-        first = eng.step_index % depth  # the slot the block's first step writes
-        eng.run(k1 - k0, frames=None if frames is None else frames[k0:k1])
+    for k0, k1, first in run_blocks(eng, nsteps, frames, on_block):
         eng.catchment_series("M_total", first=first, count=k1 - k0, out=buf[k0:k1])
         if after_block is not None:
             after_block(k0, k1, first)
