@@ -34,7 +34,12 @@ oracle E_in is not finite (a zero or negative humidity: log of it) are outside
 the probe's linear range and carry no parity assertion; they stay in the sweep
 for the layout-identity assertion.
 
-CPU-importable: the engine is imported only inside gpu_probe.
+The one-catchment kernels (k_cell, k_cell_many) run their own restatement of
+the fp64 step; gpu_probe_one_cell steps a deterministic sample of each sweep's
+(point, step) pairs (one_cell_sample) through them, one launch per pair, from
+the same injected state and with the same uniform records as gpu_probe.
+
+CPU-importable: the engine is imported only inside the gpu_* and update_* functions.
 """
 
 from __future__ import annotations
@@ -62,6 +67,13 @@ OUTS = ("h_snow", "SM", "h_ice", "IM", "M_total", "RH")
 FORMS = [(f"{n}{'-sat' if sat else ''}-{'nansafe' if ns else 'plain'}", eng, sat, ns)
          for n, eng in (("f32", "float32"), ("fluxf64", FLUX_F64_ENGINE)) for sat in (False, True) for ns in (True, False)]
 FORMS.append(("f64", "float64", False, None))
+FORMS.append(("f64-sat", "float64", True, None))
+
+ONE_CELL_KERNELS = ("k_cell", "k_cell_many")  # tfg_update, tfg_update_many: the drop-in path's single steps
+IN_ORDER = ("P_air", "Hum_sp", "P", "T_air", "uz")  # tfg_update / tfg_update_many input order
+OUT_ROW = {"h_snow": 0, "SM": 2, "h_ice": 3, "IM": 5, "M_total": 6, "RH": 7}  # rows of their [8][1] output block
+SAMPLE_SEED = 20260101  # one_cell_sample's; the same as layouts'
+MANY_POOL = 96          # handles of a k_cell_many probe: each batch steps them all in one launch
 
 
 def f32(x):
@@ -504,3 +516,205 @@ def first_lane(layout, n_points):
     first[lay[::-1]] = np.arange(len(lay))[::-1]
     assert (first >= 0).all()
     return first
+
+
+# ------------------------------------------------------------------------------------------- the one-cell kernels' probe
+def with_steps(s, steps):
+    """The sweep with only the steps `steps` (indices, in that order)."""
+    sub = SimpleNamespace(**vars(s))
+    sub.jd, sub.th, sub.night = s.jd[steps], s.th[steps], s.night[steps]
+    return sub
+
+
+def pad_to_waves(points):
+    """Point indices padded to whole waves with repeats of the last, as layouts() pads."""
+    a = np.asarray(points, np.int64)
+    return np.concatenate([a, np.full((-len(a)) % WAVE, a[-1])])
+
+
+def cb_near(s):
+    """[steps][points] of a bracket sweep (Cb-lat*): True where the step is within C_NEAR of the point's own
+    sunrise or sunset for the step's jd, computed with _sun_offsets as sweep_c places the steps."""
+    lat = dict(O.CFG_DEFAULTS, **s.cfg)["lat"]
+    m = O.OracleGrid(s.cfg, elev=s.pts["elev"], slope=s.pts["slope"], aspect=s.pts["aspect"], h0_snow=0.0, h0_ice=0.0,
+                     h0_swe=0.0, h0_iwe=0.0)
+    near = np.zeros((len(s.th), s.n), bool)
+    for jd in np.unique(s.jd[1:]):
+        ks = np.nonzero(s.jd == jd)[0]
+        ks = ks[ks > 0]
+        sr, ss = _sun_offsets(lat, jd, m.alpha, m.beta)
+        th = s.th[ks][:, None]
+        with np.errstate(invalid="ignore"):
+            near[ks] = (np.abs(th - sr[None, :]) <= C_NEAR) | (np.abs(th - ss[None, :]) <= C_NEAR)
+    return near
+
+
+@lru_cache(maxsize=None)
+def one_cell_sample(sweep: str, satterlund: bool = False):
+    """The (point, step) pairs [N][2] of a sweep that the one-cell kernels step one launch each, sorted by
+    point, then step; deterministic (default_rng(SAMPLE_SEED)).
+
+      A         both steps of one point, drawn at random, of every combination present of classes() value x
+                surface (A_SURF) x wind (A_UZ) x (T_air > 0), and of every point with T_air == 0 at uz = 3
+      B-Trs*    every point (one step)
+      C-lat*    the dark step and the 48 hourly steps of days 171 and 354, for every albedo state at slope
+                0.5 and aspects 0, 90, 180 and 270
+      Cb-lat*   every (slope, aspect) cell at albedo state 5 (aged snow in warm air): the dark step and the
+                steps within C_NEAR of that cell's own sunrise or sunset (cb_near)"""
+    s = get_sweep(sweep, satterlund)
+    rng = np.random.default_rng(SAMPLE_SEED)
+    S = len(s.th)
+    if sweep == "A":
+        ref = reference(sweep, satterlund)
+        _, surf = np.unique(np.stack([s.pts["h_snow"], s.pts["h_ice"]]), axis=1, return_inverse=True)
+        key = np.stack([classes(s, ref), surf.reshape(-1), s.uz_id, (s.pts["T_air"] > 0).astype(np.int64)])
+        _, combo = np.unique(key, axis=1, return_inverse=True)
+        combo = combo.reshape(-1)
+        pts = [int(rng.choice(np.nonzero(combo == c)[0])) for c in range(combo.max() + 1)]
+        pts += list(np.nonzero((s.pts["T_air"] == 0) & (s.pts["uz"] == 3.0))[0])
+        pairs = [(p, k) for p in np.unique(pts) for k in range(S)]
+    elif sweep.startswith("B"):
+        pairs = [(p, 0) for p in range(s.n)]
+    elif sweep.startswith("Cb"):
+        near = cb_near(s)
+        state5 = np.nonzero(s.pts["h_snow"] > 0)[0]  # C_BRACKET_ALB = (5, 8): state 8 is bare ice
+        pairs = [(p, k) for p in state5 for k in [0] + list(np.nonzero(near[:, p])[0])]
+    else:
+        days = [1 + 24 * C_DAYS.index(d) for d in (171.0, 354.0)]
+        steps = [0] + [d0 + h for d0 in days for h in range(24)]
+        sel = np.nonzero((s.pts["slope"] == 0.5) & np.isin(s.pts["aspect"], (0.0, 90.0, 180.0, 270.0)))[0]
+        pairs = [(p, k) for p in sel for k in steps]
+    out = np.array(sorted(set((int(p), int(k)) for p, k in pairs)), dtype=np.int64).reshape(-1, 2)
+    out.setflags(write=False)
+    return out
+
+
+def one_cell_engine(cfg, n_catch: int = 1, cell_catchment: int | None = None, shared_stream: bool = False):
+    """A 1 x 1 float64 handle with one frame and one history slot, initialised with no snow and no ice
+    (inject_point sets the point).  cell_catchment: the catchment (of n_catch) the cell sits in.
+    init_state() runs before any static is set and is not repeated when inject_point changes them: set_field
+    of elev, slope or aspect marks the handle's static planes stale, and the next launch derives them again
+    (the C sweeps' bits against the grid kernel depend on it)."""
+    e = make_engine(cfg, 1, 1, "float64", n_frames=1, hist_depth=1, n_catch=n_catch)
+    try:
+        if cell_catchment is not None:
+            e.set_field("catch_id", np.array([cell_catchment], dtype=np.int32))
+        e.init_state()
+        if shared_stream:
+            from topoflow_glacier.bmi import bmi_topoflow_glacier as B
+
+            e.set_stream(B._shared_stream(0))
+    except Exception:
+        e.close()
+        raise
+    return e
+
+
+def inject_point(e, s, i: int, statics: bool = True) -> None:
+    """Point i of the sweep into a one-cell handle: its statics (unless the handle holds them), the injected
+    state (ECC0 in both cold contents) and window slot 1."""
+    one = lambda a: np.ascontiguousarray(a[i:i + 1], dtype=np.float64)  # noqa: E731
+    if statics:
+        for k in ("elev", "slope", "aspect"):
+            e.set_field(k, one(s.pts[k]))
+    ecc = np.full(1, ECC0)
+    for name in STATE:
+        e.set_field(name, ecc if name in ("Eccs", "Ecci") else one(s.pts[name]))
+    e.set_field("window", one(s.pts["ring"]), index=1)
+
+
+def point_inputs(s, i: int) -> np.ndarray:
+    return np.array([[s.pts[v][i]] for v in IN_ORDER], dtype=np.float64)
+
+
+def probe_uniform(clock, k: int):
+    """Step k's uniform record with frame = hist = slot = 0, as gpu_probe makes it."""
+    u = clock.uniforms(k, 1)
+    u["frame"], u["hist"], u["slot"] = 0, 0, 0
+    return np.ascontiguousarray(u)
+
+
+def update_one(e, values, u, out) -> None:
+    """tfg_update (k_cell) with the caller's uniform record."""
+    from topoflow_glacier import _native as nat
+
+    e._chk(e.lib.tfg_update(e.h, 0, values.ctypes.data, nat.F64, u.ctypes.data, out.ctypes.data, nat.F64, 1))
+
+
+def update_batch(engines, values, us, outs) -> None:
+    """tfg_update_many (k_cell_many, one launch) with the caller's uniform records, as UpdateBatch.run calls it."""
+    import ctypes
+
+    from topoflow_glacier import _native as nat
+
+    m = len(engines)
+    arr = ctypes.c_void_p * m
+    nat.check(engines[0].lib.tfg_update_many(arr(*[e.h.value for e in engines]), m, arr(*[v.ctypes.data for v in values]),
+                                             arr(*[u.ctypes.data for u in us]), arr(*[o.ctypes.data for o in outs])))
+
+
+def gpu_probe_one_cell(s, kernel: str, satterlund: bool, point_steps, handles: list | None = None):
+    """The (point, step) pairs `point_steps` [N][2], each one launch of a one-cell kernel from the injected
+    state (the read_depths = 1 entry: the depths are set before every step): per name in READ + OUTS + E_in +
+    cold, [N] as gpu_probe returns them per (step, lane); READ from the handle's state, OUTS from the
+    call's output block.  "k_cell": one handle, reused over the points; "k_cell_many": up to MANY_POOL
+    handles on the BMI's shared stream, each holding a run of consecutive pairs, all stepped once per
+    launch.  `handles` (a list) receives, per handle, (diagnostics [1][6], the P it was fed, in order, and
+    T_air)."""
+    assert kernel in ONE_CELL_KERNELS, kernel
+    ps = np.asarray(point_steps, np.int64).reshape(-1, 2)
+    N = len(ps)
+    cfg = dict(s.cfg, SATTERLUND=satterlund)
+    clock = probe_clock(s)
+    urec = {int(k): probe_uniform(clock, int(k)) for k in np.unique(ps[:, 1])}
+    res = {k: np.empty(N) for k in READ + OUTS}
+    m = 1 if kernel == "k_cell" else min(N, MANY_POOL)
+    per = -(-N // m)  # handle j steps pairs j per ... (j + 1) per - 1, one per launch
+    engines, fed = [], [[] for _ in range(m)]
+    try:
+        for _ in range(m):
+            engines.append(one_cell_engine(cfg, shared_stream=kernel == "k_cell_many"))
+        holds = [-1] * m
+        outs = [np.empty((8, 1)) for _ in range(m)]
+        for b in range(per):
+            js = [j for j in range(m) if j * per + b < min(N, (j + 1) * per)]
+            vals = []
+            for j in js:
+                i, k = ps[j * per + b]
+                inject_point(engines[j], s, i, statics=holds[j] != i)
+                holds[j] = i
+                vals.append(point_inputs(s, i))
+                fed[j].append((s.pts["P"][i], s.pts["T_air"][i]))
+            us = [urec[int(ps[j * per + b, 1])] for j in js]
+            if kernel == "k_cell":
+                update_one(engines[0], vals[0], us[0], outs[0])
+            else:
+                update_batch([engines[j] for j in js], vals, us, [outs[j] for j in js])
+            for j in js:
+                q = j * per + b
+                for name in READ:
+                    res[name][q] = engines[j].get_field(name)[0]
+                for name in OUTS:
+                    res[name][q] = outs[j][OUT_ROW[name], 0]
+        if handles is not None:
+            handles += [(e.diagnostics(), np.array([f[0] for f in fd]), np.array([f[1] for f in fd]))
+                        for e, fd in zip(engines, fed)]
+    finally:
+        for e in engines:
+            e.close()
+    sl = SimpleNamespace(from_ecci=s.from_ecci[ps[:, 0]], cold_ok=s.cold_ok[ps[:, 0]])
+    res["E_in"], res["cold"] = recover(sl, res["Eccs"], res["Ecci"])
+    return res
+
+
+def fed_diagnostics(cfg, P, T_air):
+    """vol_P, vol_PR, vol_PS, P_max of a handle fed the steps (P, T_air) in order: the fp64 sums, in that
+    order, of P da dt (:558-624; da in m2, dt in the config's hours, as harness.catchment_diag has them)."""
+    c = dict(O.CFG_DEFAULTS)
+    c.update(cfg)
+    da_m2, dt = np.float64(c["da"]) * 1e6, np.float64(c["dt"])
+    tot = np.zeros(3)
+    for p, t in zip(P, T_air):
+        rain = 1.0 if t > c["T_rain_snow"] else 0.0
+        tot += np.array([p, p * rain, p * (1.0 - rain)]) * da_m2 * dt
+    return np.array([tot[0], tot[1], tot[2], np.max(P) if len(P) else 0.0])

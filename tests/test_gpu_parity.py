@@ -327,45 +327,93 @@ def test_fusion_is_invisible(engine):
         assert np.array_equal(a[1][v], b[1][v]) and np.array_equal(a[1][v], c[1][v]), v
 
 
+def _one_cell_trajectories(cfg, static, forcing, c, nsteps):
+    """Cell c of a grid's inputs through the one-cell kernels: (outputs [nsteps] per name and final state of
+    k_cell_run (tfg_step, 24 steps per launch), the same of k_cell (update_io, one step per call))."""
+    order = ("P_air", "Hum_sp", "P", "T_air", "uz")  # tfg_update / update_io input order
+    st1 = {k: v[c:c + 1] for k, v in static.items()}
+    f1 = {k: v[:, c:c + 1] for k, v in forcing.items()}
+    run = gpu_run_fields(cfg, st1, f1, 1, 1, "float64", nsteps, fuse_steps=24)
+    e = make_engine(cfg, 1, 1, "float64", n_frames=1, hist_depth=1)
+    try:
+        for k in ("elev", "slope", "aspect"):
+            e.set_field(k, st1[k])
+        for k in ("h_snow", "h_ice", "h_swe", "h_iwe"):
+            e.set_field(k, st1["h0_" + k[2:]])
+        e.init_state()
+        out = np.empty((8, 1))
+        upd = {v: [] for v in HIST}
+        for k in range(nsteps):
+            e.update_io(np.array([[f1[n][k, 0]] for n in order], dtype=np.float64), out)
+            for j, v in enumerate(("h_snow", "h_swe", "SM", "h_ice", "h_iwe", "IM", "M_total", "RH")):
+                if v in upd:
+                    upd[v].append(out[j, 0])
+        state = {v: e.get_field(v) for v in ("h_swe", "h_iwe", "Eccs", "Ecci", "albedo", "n")}
+    finally:
+        e.close()
+    return ({v: run[0][v][:, 0] for v in HIST}, {v: run[1][v][0] for v in state}), \
+        ({v: np.array(upd[v]) for v in HIST}, {v: state[v][0] for v in state})
+
+
 @pytest.mark.gpu
-def test_one_cell_kernels_equal_the_grid_kernel():
+@pytest.mark.parametrize("name", ["grid64", "satterlund", "params", "dt2", "dt_quarter"])
+def test_one_cell_kernels_equal_the_grid_kernel(name):
     """A one-cell fp64 handle runs k_cell (tfg_update, the BMI's update()) or
     k_cell_run (tfg_step: update_until, bulk runs), which batch the step's
     transcendental calls across the wave's lanes; a grid runs
     k_fused<double, true, ...> with one cell per lane.  Same arithmetic, same
-    bits: cells of the grid64 fixture run both ways over 100 steps."""
-    from tests.harness import make_engine
+    bits: the first, the last and two interior cells of each fixture (the
+    default and Satterlund's vapour formulas, other parameters, dt = 2 h and
+    0.25 h) run both ways over 100 steps.  After the first step these are the
+    kernels' depth-derived entry (read_depths = 0)."""
+    g = load_golden(name)
+    n, nsteps = g["ncell"], min(100, g["nsteps"])
+    forcing = {k: v[:nsteps] for k, v in g["forcing"].items()}
+    ny, nx = (8, 8) if n == 64 else (1, n)
+    grid = gpu_run_fields(g["cfg"], g["static"], forcing, ny, nx, "float64", nsteps, fuse_steps=24)
+    cells = (0, 17, 42, 63) if n == 64 else sorted({0, n // 3, (2 * n) // 3, n - 1})
+    assert len(cells) == min(4, n) and cells[0] == 0 and cells[-1] == n - 1
+    for c in cells:
+        for kernel, (outs, state) in zip(("k_cell_run", "k_cell"), _one_cell_trajectories(g["cfg"], g["static"], forcing, c, nsteps)):
+            for v in HIST:
+                assert np.array_equal(outs[v], grid[0][v][:, c]), (c, v, kernel)
+            for v in state:
+                assert state[v] == grid[1][v][c], (c, v, kernel)
 
+
+@pytest.mark.gpu
+def test_one_cell_kernels_propagate_nan_forcing_like_the_grid_kernel():
+    """The NaN edits of test_engine_propagates_nan_forcing_like_the_reference (a NaN T_air under
+    precipitation, a NaN P that freezes n while its slot is in the window, a NaN Hum_sp, uz and P_air, one
+    cell each) through k_cell_run and k_cell: every edited cell has NaN at the grid kernel's positions, the
+    bits of its finite values, and its state, the frozen n included.  The grid side is held to the
+    reference by that test."""
     g = load_golden("grid64")
+    cells = slice(8, 16)
     nsteps = 100
-    grid = gpu_run_fields(g["cfg"], g["static"], g["forcing"], 8, 8, "float64", nsteps, fuse_steps=24)
-    order = ("P_air", "Hum_sp", "P", "T_air", "uz")  # tfg_update / update_io input order
-    for c in (0, 17, 42, 63):
-        static = {k: v[c:c + 1] for k, v in g["static"].items()}
-        forcing = {k: v[:, c:c + 1] for k, v in g["forcing"].items()}
-        run = gpu_run_fields(g["cfg"], static, forcing, 1, 1, "float64", nsteps, fuse_steps=24)
-        e = make_engine(g["cfg"], 1, 1, "float64", n_frames=1, hist_depth=1)
-        try:
-            for k in ("elev", "slope", "aspect"):
-                e.set_field(k, static[k])
-            for k in ("h_snow", "h_ice", "h_swe", "h_iwe"):
-                e.set_field(k, static["h0_" + k[2:]])
-            e.init_state()
-            out = np.empty((8, 1))
-            upd = {v: [] for v in HIST}
-            for k in range(nsteps):
-                e.update_io(np.array([[forcing[n][k, 0]] for n in order], dtype=np.float64), out)
-                for j, v in enumerate(("h_snow", "h_swe", "SM", "h_ice", "h_iwe", "IM", "M_total", "RH")):
-                    if v in upd:
-                        upd[v].append(out[j, 0])
-            state = {v: e.get_field(v) for v in ("h_swe", "h_iwe", "Eccs", "Ecci", "albedo", "n")}
-        finally:
-            e.close()
-        for v in HIST:
-            assert np.array_equal(run[0][v][:, 0], grid[0][v][:, c]), (c, v, "k_cell_run")
-            assert np.array_equal(np.array(upd[v]), grid[0][v][:, c]), (c, v, "k_cell")
-        for v in state:
-            assert run[1][v][0] == grid[1][v][c] == state[v][0], (c, v)
+    forcing = {k: np.array(v[:nsteps, cells], copy=True) for k, v in g["forcing"].items()}
+    static = {k: np.asarray(v[cells]) for k, v in g["static"].items()}
+    forcing["T_air"][3, 0] = np.nan
+    forcing["P"][3, 0] = max(forcing["P"][3, 0], 2e-4)
+    forcing["P"][5, 1] = np.nan
+    forcing["Hum_sp"][2, 2] = np.nan
+    forcing["uz"][7, 3] = np.nan
+    forcing["P_air"][9, 4] = np.nan
+    grid = gpu_run_fields(g["cfg"], static, forcing, 1, 8, "float64", nsteps)
+    assert np.isnan(grid[0]["M_total"][-1, :5]).all() and np.isfinite(grid[0]["M_total"][-1, 5:]).all()
+
+    def same(a, b):  # NaN where the other is, else the same bits
+        a, b = np.atleast_1d(np.asarray(a, np.float64)), np.atleast_1d(np.asarray(b, np.float64))
+        return bool(np.all((np.isnan(a) & np.isnan(b)) | (a.view(np.int64) == b.view(np.int64))))
+
+    for c in range(5):  # the five edited cells
+        for kernel, (outs, state) in zip(("k_cell_run", "k_cell"), _one_cell_trajectories(g["cfg"], static, forcing, c, nsteps)):
+            for v in HIST:
+                assert same(outs[v], np.ascontiguousarray(grid[0][v][:, c])), (c, v, kernel)
+            for v in state:
+                assert same(state[v], grid[1][v][c]), (c, v, kernel)
+        if c == 1:
+            assert abs(grid[1]["n"][1] * 86400.0 - (nsteps - 72)) < 1e-6  # frozen for the 72 steps
 
 
 @pytest.mark.parametrize("fuse,chunks,n_catch", [(96, None, 1), (100, None, 1), (150, None, 1), (192, [192, 58], 1),

@@ -1,5 +1,7 @@
 """The one-step energy probe (tests/step_probe.py) on the oracle alone: the method returns the oracle's
-own terms, and every sweep meets the conditions the GPU test (test_gpu_step_terms.py) relies on.  CPU only."""
+own terms, and every sweep meets the conditions the GPU test (test_gpu_step_terms.py) relies on; the sample
+the one-cell kernels step (one_cell_sample, test_gpu_one_cell_terms.py) is deterministic and holds every
+set it is meant to.  CPU only."""
 
 from __future__ import annotations
 
@@ -144,6 +146,120 @@ def test_the_sweeps_reach_the_edges_they_are_built_for():
                     assert np.any((den < 0) & (T + RH > 0) & b.snowing)
                 assert np.any(RH < 0) and np.any(RH > 5) and np.any(RH > 11) and np.any((RH > 0) & (RH < 5))
     assert float(np.float32(50.2)) > 50.2  # so the engine's threshold is the float below: the rounded-down case
+
+
+# ------------------------------------------------------------------------------------------- the one-cell sample
+def test_one_cell_sample_is_deterministic():
+    for name, sat in CASES:
+        a = SP.one_cell_sample(name, sat).copy()
+        SP.one_cell_sample.cache_clear()
+        b = SP.one_cell_sample(name, sat)
+        assert a.shape[1] == 2 and np.array_equal(a, b), name
+        assert len(np.unique(a, axis=0)) == len(a) and np.array_equal(a, a[np.lexsort((a[:, 1], a[:, 0]))])
+        s = SP.get_sweep(name, sat)
+        assert a[:, 0].min() >= 0 and a[:, 0].max() < s.n and a[:, 1].min() >= 0 and a[:, 1].max() < len(s.th)
+
+
+def _pairs(name, sat):
+    return {(int(p), int(k)) for p, k in SP.one_cell_sample(name, sat)}
+
+
+@pytest.mark.parametrize("sat", [False, True])
+def test_one_cell_sample_of_sweep_a_holds_every_combination(sat):
+    """Both steps of at least one point of every combination, present in the sweep, of classes() value x
+    surface x wind x (T_air > 0), and of every point with T_air == 0 at uz = 3."""
+    s, ref, have = SP.get_sweep("A", sat), SP.reference("A", sat), _pairs("A", sat)
+    both = np.array([(p, 0) in have and (p, 1) in have for p in range(s.n)])
+    surf = np.full(s.n, -1)
+    for j, (hs, hi) in enumerate(SP.A_SURF):
+        surf[(s.pts["h_snow"] == SP.f32(hs)) & (s.pts["h_ice"] == SP.f32(hi))] = j
+    wind = np.full(s.n, -1)
+    for j, u in enumerate(SP.A_UZ):
+        wind[s.pts["uz"] == SP.f32(u)] = j
+    assert surf.min() == 0 and wind.min() == 0
+    assert set(surf) == set(range(7)) and set(wind) == set(range(6))
+    key = np.stack([SP.classes(s, ref), surf, wind, (s.pts["T_air"] > 0).astype(int)])
+    combos = {tuple(c) for c in key.T}
+    assert {tuple(c) for c in key[:, both].T} == combos and len(combos) > 7 * 6 * 2
+    assert np.all(both[(s.pts["T_air"] == 0) & (s.pts["uz"] == 3.0)]) and np.any((s.pts["T_air"] == 0) & (s.pts["uz"] == 3.0))
+
+
+@pytest.mark.parametrize("sat", [False, True])
+@pytest.mark.parametrize("name,n,n_nan", [("B-Trs0", 816, 88), ("B-Trs50.2", 1488, 152)])
+def test_one_cell_sample_of_sweep_b_is_the_whole_sweep(name, n, n_nan, sat):
+    s, ref = SP.get_sweep(name, sat), SP.reference(name, sat)
+    assert s.n == n and len(s.th) == 1 and _pairs(name, sat) == {(p, 0) for p in range(n)}
+    assert int(np.isnan(ref["E_in"]).sum()) == n_nan
+
+
+@pytest.mark.parametrize("lat", [0.0, 46.8, 70.0])
+def test_one_cell_sample_of_sweep_c_holds_the_two_solstice_days(lat):
+    """The dark step plus the 48 hourly steps of days 171 and 354, for all eleven albedo states, at slope 0.5
+    and aspects 0, 90, 180 and 270."""
+    name = f"C-lat{lat:g}"
+    s, have = SP.get_sweep(name), _pairs(name, False)
+    assert _pairs(name, True) == have
+    steps = [0] + [k for k in range(1, len(s.th)) if np.floor(s.jd[k]) in (171.0, 354.0)]
+    assert len(steps) == 49 and s.night[0] and not s.night[steps[1:]].any()
+    assert {(s.jd[k], s.th[k]) for k in steps[1:]} == {(d + h / 24.0, h - 12.0 + 0.37) for d in (171.0, 354.0) for h in range(24)}
+    state = np.array(list(zip(s.pts["n"], s.pts["T_air"], s.pts["h_snow"], s.pts["ring"], s.pts["P"])))
+    for aspect in (0.0, 90.0, 180.0, 270.0):
+        for alb in SP.C_ALB:
+            want = np.array([alb[0], SP.f32(alb[1]), SP.f32(alb[2]), alb[3], SP.f32(alb[4])])  # n and the window stay fp64
+            p = np.nonzero((s.pts["slope"] == 0.5) & (s.pts["aspect"] == aspect) & np.all(state == want, axis=1))[0]
+            assert len(p) == 1, (aspect, alb)
+            assert all((int(p[0]), k) in have for k in steps), (aspect, alb)
+
+
+@pytest.mark.parametrize("lat", [0.0, 46.8, 70.0])
+def test_one_cell_sample_of_sweep_cb_brackets_each_cells_own_times(lat):
+    """All 96 (slope, aspect) cells at albedo state 5, each with the dark step and every step within C_NEAR
+    of its own sunrise or sunset, and steps on both sides of both times on every day the oracle gives it
+    one (a finite offset)."""
+    name = f"Cb-lat{lat:g}"
+    s, have = SP.get_sweep(name), _pairs(name, False)
+    assert _pairs(name, True) == have
+    m = O.OracleGrid(s.cfg, elev=s.pts["elev"], slope=s.pts["slope"], aspect=s.pts["aspect"], h0_snow=0.0, h0_ice=0.0,
+                     h0_swe=0.0, h0_iwe=0.0)
+    n5, T5, h5 = SP.C_ALB[5][:3]
+    cells = np.nonzero((s.pts["n"] == n5) & (s.pts["T_air"] == T5) & (s.pts["h_snow"] == h5))[0]
+    assert {(s.pts["slope"][p], s.pts["aspect"][p]) for p in cells} == \
+        {(float(np.float32(a)), float(b)) for a in SP.C_SLOPES for b in SP.C_ASPECTS} and len(cells) == 96
+    assert {p for p, _ in have} == set(cells)
+    sides = 0
+    for p in cells:
+        ks = np.array(sorted(k for q, k in have if q == p))
+        assert ks[0] == 0 and len(ks) < 60
+        for day in SP.C_DAYS:
+            jn = SP.bracket_jd(day)
+            th = s.th[ks][s.jd[ks] == jn]
+            for t in (O.sunrise_offset_slope(lat, jn, m.alpha[p:p + 1], m.beta[p:p + 1])[0],
+                      O.sunset_offset_slope(lat, jn, m.alpha[p:p + 1], m.beta[p:p + 1])[0]):
+                if not np.isfinite(t):
+                    continue
+                d = th - t
+                assert np.any((d > 0) & (d <= SP.C_NEAR)) and np.any((d < 0) & (d >= -SP.C_NEAR)), (p, day, t)
+                # every step of the sweep that near is in the sample
+                near = np.nonzero((s.jd == jn) & (np.abs(s.th - t) <= SP.C_NEAR))[0]
+                assert set(near) <= set(ks)
+                sides += 1
+    assert sides == 96 * 4 * 2
+
+
+@pytest.mark.parametrize("name,sat", CASES, ids=IDS)
+def test_one_cell_sample_keeps_linear_points_in_every_stratum(name, sat):
+    """Every stratum of the sweep keeps at least one sampled pair in the probe's linear range for E_in, and,
+    where the sweep has snowfall to read a cold content from, at least one for the cold content."""
+    s, ref, ps = SP.get_sweep(name, sat), SP.reference(name, sat), SP.one_cell_sample(name, sat)
+    lin = SP.linear(s, ref)
+    P, K = ps[:, 0], ps[:, 1]
+    for label, steps, pts in SP.strata(s):
+        mine = steps[K] & pts[P] & lin[K, P]
+        assert mine.any(), label
+        if SP.stratum_block(lin & s.cold_ok[None, :], steps, pts).any():
+            assert (mine & s.cold_ok[P]).any(), label
+    if name.startswith("B"):
+        assert s.cold_ok.any()
 
 
 @pytest.mark.parametrize("name", list(SP.SWEEPS))
