@@ -39,6 +39,10 @@ the fp64 step; gpu_probe_one_cell steps a deterministic sample of each sweep's
 (point, step) pairs (one_cell_sample) through them, one launch per pair, from
 the same injected state and with the same uniform records as gpu_probe.
 
+The other half of the step, from E_in and the state to the melt rates, depths and cold contents, has its
+own cases at the end of this file ("melt states": melt_case, meltout_case, melt_tail), stepped from
+injected cold contents of the cell's own size instead of ECC0 (gpu_probe's and gpu_probe_one_cell's `ecc`).
+
 CPU-importable: the engine is imported only inside the gpu_* and update_* functions.
 """
 
@@ -439,7 +443,13 @@ def layouts(s, ref, seed: int = 20260101):
     point layout[i].  sorted: each class padded to whole waves (with repeats of its last point), so every
     wave is uniform.  interleaved: a random permutation (padded), then, per class, up to four waves of 63
     points of other classes with ONE lane of that class at a random position."""
-    cls = classes(s, ref)
+    return layouts_of(classes(s, ref), seed)
+
+
+def layouts_of(cls, seed: int = 20260101):
+    """layouts() for any per-point class array."""
+    cls = np.asarray(cls)
+    s = SimpleNamespace(n=len(cls))
     rng = np.random.default_rng(seed)
 
     def pad(a):
@@ -472,40 +482,59 @@ def probe_clock(s):
     return _Clock(c["start_time"], c["dt"], c["lat"], c["lon"], c["time_zone"])
 
 
-def gpu_probe(s, engine: str, satterlund: bool, nan_safe, layout):
+def gpu_probe(s, engine: str, satterlund: bool, nan_safe, layout, ecc=None, extra=(), follow: int = 0, catch=None):
     """One engine step per sweep step on the grid `layout` (1 x len(layout)), state re-injected before
     each; returns, per name in READ + OUTS, [steps][len(layout)] as read back, and E_in, cold by recover().
     The step writes window slot 0 each time and slot 1 holds the snowfall already in the window, so the
-    window's total is the same at every step."""
+    window's total is the same at every step.
+
+    ecc = (Eccs, Ecci), per point: the injected cold contents instead of ECC0 (E_in and cold are then not
+    returned).  extra: further fields to read back.  follow: that many further steps after each, from
+    the state the step left (same clock, forcing and window slot), read back as "<name>@<j>".  catch =
+    (ids per point, n_catch): a catchment raster; the diagnostics are reset before every injected step
+    and returned as "diag" [steps][n_catch][6] after it and as "diag@<j>"."""
     lay = np.asarray(layout)
     n = len(lay)
     p = {k: np.ascontiguousarray(v[lay]) for k, v in s.pts.items()}
-    sl = SimpleNamespace(from_ecci=s.from_ecci[lay], cold_ok=s.cold_ok[lay])
     cfg = dict(s.cfg, SATTERLUND=satterlund)
     clock = probe_clock(s)
-    e = make_engine(cfg, 1, n, engine, n_frames=1, hist_depth=1, fuse_steps=1)
-    out = {k: np.empty((len(s.th), n)) for k in READ + OUTS + ("E_in", "cold")}
+    names = READ + OUTS + tuple(extra)
+    e = make_engine(cfg, 1, n, engine, n_frames=1, hist_depth=1, fuse_steps=1, n_catch=1 if catch is None else catch[1])
+    out = {k: np.empty((len(s.th), n)) for k in names + tuple(f"{v}@{j}" for v in names for j in range(1, follow + 1))}
+    if catch is not None:
+        out.update({k: np.empty((len(s.th), catch[1], 6)) for k in ["diag"] + [f"diag@{j}" for j in range(1, follow + 1)]})
     try:
         for k in ("elev", "slope", "aspect", "h_snow", "h_ice", "h_swe", "h_iwe"):
             e.set_field(k, p[k])
+        if catch is not None:
+            e.set_field("catch_id", np.ascontiguousarray(np.asarray(catch[0])[lay], dtype=np.int32))
         e.init_state()
         if nan_safe is not None:
             e.set_step_form(bool(nan_safe))
         e.set_inputs(np.stack([p[v] for v in ("P_air", "Hum_sp", "P", "T_air", "uz")]), 0)
         e.set_field("window", p["ring"], index=1)
-        ecc = np.full(n, ECC0)
+        inj = {"Eccs": np.full(n, ECC0), "Ecci": np.full(n, ECC0)} if ecc is None else \
+            {"Eccs": np.ascontiguousarray(ecc[0][lay]), "Ecci": np.ascontiguousarray(ecc[1][lay])}
         for k in range(len(s.th)):
             for name in STATE:
-                e.set_field(name, ecc if name in ("Eccs", "Ecci") else p[name])
+                e.set_field(name, inj[name] if name in inj else p[name])
+            if catch is not None:
+                e.reset_diagnostics()
             u = clock.uniforms(k, 1)
             u["frame"], u["hist"], u["slot"] = 0, 0, 0
-            e.run(1, uniforms=u)
-            e.sync()
-            for name in READ + OUTS:
-                out[name][k] = e.get_field(name)
-            out["E_in"][k], out["cold"][k] = recover(sl, out["Eccs"][k], out["Ecci"][k])
+            for j in range(follow + 1):
+                e.run(1, uniforms=u)
+                e.sync()
+                tag = f"@{j}" if j else ""
+                for name in names:
+                    out[name + tag][k] = e.get_field(name)
+                if catch is not None:
+                    out["diag" + tag][k] = e.diagnostics()
     finally:
         e.close()
+    if ecc is None:
+        sl = SimpleNamespace(from_ecci=s.from_ecci[lay], cold_ok=s.cold_ok[lay])
+        out["E_in"], out["cold"] = recover(sl, out["Eccs"], out["Ecci"])
     return out
 
 
@@ -610,16 +639,16 @@ def one_cell_engine(cfg, n_catch: int = 1, cell_catchment: int | None = None, sh
     return e
 
 
-def inject_point(e, s, i: int, statics: bool = True) -> None:
+def inject_point(e, s, i: int, statics: bool = True, ecc=None) -> None:
     """Point i of the sweep into a one-cell handle: its statics (unless the handle holds them), the injected
-    state (ECC0 in both cold contents) and window slot 1."""
+    state (ECC0 in both cold contents, or ecc = (Eccs, Ecci) per point) and window slot 1."""
     one = lambda a: np.ascontiguousarray(a[i:i + 1], dtype=np.float64)  # noqa: E731
     if statics:
         for k in ("elev", "slope", "aspect"):
             e.set_field(k, one(s.pts[k]))
-    ecc = np.full(1, ECC0)
+    inj = {"Eccs": np.full(1, ECC0), "Ecci": np.full(1, ECC0)} if ecc is None else {"Eccs": one(ecc[0]), "Ecci": one(ecc[1])}
     for name in STATE:
-        e.set_field(name, ecc if name in ("Eccs", "Ecci") else one(s.pts[name]))
+        e.set_field(name, inj[name] if name in inj else one(s.pts[name]))
     e.set_field("window", one(s.pts["ring"]), index=1)
 
 
@@ -653,21 +682,24 @@ def update_batch(engines, values, us, outs) -> None:
                                              arr(*[u.ctypes.data for u in us]), arr(*[o.ctypes.data for o in outs])))
 
 
-def gpu_probe_one_cell(s, kernel: str, satterlund: bool, point_steps, handles: list | None = None):
+def gpu_probe_one_cell(s, kernel: str, satterlund: bool, point_steps, handles: list | None = None, ecc=None, extra=(),
+                       follow: int = 0):
     """The (point, step) pairs `point_steps` [N][2], each one launch of a one-cell kernel from the injected
     state (the read_depths = 1 entry: the depths are set before every step): per name in READ + OUTS + E_in +
     cold, [N] as gpu_probe returns them per (step, lane); READ from the handle's state, OUTS from the
     call's output block.  "k_cell": one handle, reused over the points; "k_cell_many": up to MANY_POOL
     handles on the BMI's shared stream, each holding a run of consecutive pairs, all stepped once per
     launch.  `handles` (a list) receives, per handle, (diagnostics [1][6], the P it was fed, in order, and
-    T_air)."""
+    T_air).  ecc, extra: as gpu_probe's (extra: further state fields).  follow: that many further steps of
+    each pair on the same handle, from the state its own step left (no injection; same inputs and uniform
+    record), read back as "<name>@<j>"."""
     assert kernel in ONE_CELL_KERNELS, kernel
     ps = np.asarray(point_steps, np.int64).reshape(-1, 2)
     N = len(ps)
     cfg = dict(s.cfg, SATTERLUND=satterlund)
     clock = probe_clock(s)
     urec = {int(k): probe_uniform(clock, int(k)) for k in np.unique(ps[:, 1])}
-    res = {k: np.empty(N) for k in READ + OUTS}
+    res = {k + (f"@{f}" if f else ""): np.empty(N) for k in READ + OUTS + tuple(extra) for f in range(follow + 1)}
     m = 1 if kernel == "k_cell" else min(N, MANY_POOL)
     per = -(-N // m)  # handle j steps pairs j per ... (j + 1) per - 1, one per launch
     engines, fed = [], [[] for _ in range(m)]
@@ -681,29 +713,34 @@ def gpu_probe_one_cell(s, kernel: str, satterlund: bool, point_steps, handles: l
             vals = []
             for j in js:
                 i, k = ps[j * per + b]
-                inject_point(engines[j], s, i, statics=holds[j] != i)
+                inject_point(engines[j], s, i, statics=holds[j] != i, ecc=ecc)
                 holds[j] = i
                 vals.append(point_inputs(s, i))
                 fed[j].append((s.pts["P"][i], s.pts["T_air"][i]))
             us = [urec[int(ps[j * per + b, 1])] for j in js]
-            if kernel == "k_cell":
-                update_one(engines[0], vals[0], us[0], outs[0])
-            else:
-                update_batch([engines[j] for j in js], vals, us, [outs[j] for j in js])
-            for j in js:
-                q = j * per + b
-                for name in READ:
-                    res[name][q] = engines[j].get_field(name)[0]
-                for name in OUTS:
-                    res[name][q] = outs[j][OUT_ROW[name], 0]
+            for f in range(follow + 1):
+                tag = f"@{f}" if f else ""
+                if kernel == "k_cell":
+                    update_one(engines[0], vals[0], us[0], outs[0])
+                else:
+                    update_batch([engines[j] for j in js], vals, us, [outs[j] for j in js])
+                for j in js:
+                    q = j * per + b
+                    for name in READ + tuple(extra):
+                        res[name + tag][q] = engines[j].get_field(name)[0]
+                    for name in OUTS:
+                        res[name + tag][q] = outs[j][OUT_ROW[name], 0]
+                    if f:
+                        fed[j].append((s.pts["P"][ps[q, 0]], s.pts["T_air"][ps[q, 0]]))
         if handles is not None:
             handles += [(e.diagnostics(), np.array([f[0] for f in fd]), np.array([f[1] for f in fd]))
                         for e, fd in zip(engines, fed)]
     finally:
         for e in engines:
             e.close()
-    sl = SimpleNamespace(from_ecci=s.from_ecci[ps[:, 0]], cold_ok=s.cold_ok[ps[:, 0]])
-    res["E_in"], res["cold"] = recover(sl, res["Eccs"], res["Ecci"])
+    if ecc is None:
+        sl = SimpleNamespace(from_ecci=s.from_ecci[ps[:, 0]], cold_ok=s.cold_ok[ps[:, 0]])
+        res["E_in"], res["cold"] = recover(sl, res["Eccs"], res["Ecci"])
     return res
 
 
@@ -718,3 +755,401 @@ def fed_diagnostics(cfg, P, T_air):
         rain = 1.0 if t > c["T_rain_snow"] else 0.0
         tot += np.array([p, p * rain, p * (1.0 - rain)]) * da_m2 * dt
     return np.array([tot[0], tot[1], tot[2], np.max(P) if len(P) else 0.0])
+
+
+# ------------------------------------------------------------------------------------------- melt states
+# The other half of the step: from E_in and the state to SM, IM, M_total, the new depths and cold contents
+# (:1321-1731; tfg_oracle.py:511-571).  Forcing points of sweep A crossed with a state grid built from the
+# oracle's own E_in and snowfall cold content, so that every gate of the tail is taken on both sides and
+# none is decided by rounding (melt_margins); a one-point sweep of residual depths for the melt-out bits.
+#
+# Notation.  E: the oracle's E_in = Q_sum dt at the cell's own state; cold: its snowfall cold content;
+# G = E - cold where it snows, else E; c = 3600 / (dt rho_H2O Lf) [m of water per J m-2: a depth is
+# "energy-equivalent" when divided by c]; m_s = max(E - Eccs0, 0) c and m_i = max(E - Ecci0, 0) c: the
+# depths one step could melt; S = max(|E|, |cold|, s_v dt): the scale of the parity tolerance at the cell,
+# s_v being the floor of the point's stratum in sweep A (whose dt is 1).
+#
+# Placement of the "just below / just above" values.  The parity tolerance admits an E_in error of
+# tol S in every fp32 form, and E - Eccs0 cancels: a threshold placed at m_s (1 +- 1e-3) is 1e-3 m_s away
+# from the gate, which is less than the admitted error wherever m_s < 1e-2 S c (Eccs0 itself within 1e-3
+# of G, or a point whose E at this state is below its stratum's floor).  So every +- value is placed
+# MELT_OFF max(|q|, S) from its threshold q, in energy-equivalent units (the depths': max(|q|, 0.6 S)): equal
+# to q (1 +- 1e-3) wherever |q| >= S, never closer than 0.6 MELT_OFF S, and every gate then clears MELT_MARGIN S
+# = 10 x the fp32 tolerance by construction.  A value that would be negative is 0.
+MELT_DTS = (1.0, 2.0, 0.25)
+MELT_MARGIN = 1e-4            # no gate quantity closer than this (x S) to its threshold
+MELT_OFF = 1e-3               # the +- values' distance from their threshold
+MELT_P = float(np.float32(2e-5))  # precipitation of the snowing and raining points: P dt ws << 0.03 m, so n is not reset
+DRY, SNOW, RAIN = 0, 1, 2
+# (uz of the stratum, night, sign of the sweep's E_in, T_air > 0, precipitation).  A stratum's points at or
+# above its floor are what its wind allows: warm nights and days in calm air and at 3 m/s, cold nights
+# (E_in < 0) from 0.05 m/s on; E_in > 0 in air at or below 0 degC (snowfall on a melting surface) only in
+# the calm day; no stratum has E_in < 0 in warm air at its floor, so "negative and raining" has no point.
+# The cold points are night steps: by day a cold point's E_in can be negative under snow and positive on bare
+# ground (the albedo), and a grid placed from the cell's own E_in then has no fixed point (melt_case).
+MELT_WANTS = ((0.0, True, 1, True, RAIN), (0.0, True, 1, True, DRY), (0.0, False, 1, False, SNOW), (0.0, False, 1, False, DRY),
+              (0.0, False, 1, True, RAIN), (0.05, True, -1, False, SNOW), (0.28, False, -1, False, DRY),
+              (3.0, True, -1, False, SNOW), (15.8, False, 1, True, RAIN), (40.0, True, 1, True, DRY),
+              (3.0, False, 1, True, DRY), (0.28, True, -1, False, SNOW))
+MELT_AXES = (5, 5, 6, 6)      # Eccs0, Ecci0, h_swe0, h_iwe0 values per point
+MELT_TAIL_OUT = ("SM", "IM", "M_total", "h_swe", "h_iwe", "Eccs", "Ecci", "h_snow", "h_ice", "vol_SM", "vol_IM")
+SWEEP_N = 4096                # residual depths of the melt-out sweep
+SWEEP_RANGE = (1e-9, 1e-3)    # [m], log-uniform
+
+
+def _cfgc(cfg):
+    c = dict(O.CFG_DEFAULTS)
+    c.update(cfg)
+    return c
+
+
+def melt_c(cfg):
+    """c = 3600 / (dt rho_H2O Lf), rounded as the fp32 engine's c_sm3600."""
+    c = _cfgc(cfg)
+    return 3600.0 / (np.float64(c["dt"]) * (np.float64(c["rho_H2O"]) * np.float64(c["Lf"])))
+
+
+@lru_cache(maxsize=None)
+def melt_points(satterlund: bool = False):
+    """The forcing points: per entry of MELT_WANTS one point of sweep A, drawn (default_rng(SAMPLE_SEED)) from
+    those of its stratum whose oracle |E_in| (the sweep's own state) is at least the stratum's scale_floor
+    and has the wanted sign, in air of the wanted side of 0 degC.  idx, step, kind, floor: [points]."""
+    s, ref = get_sweep("A", satterlund), reference("A", satterlund)
+    rng = np.random.default_rng(SAMPLE_SEED)
+    idx, step, kind, floor, e_ref = [], [], [], [], []
+    for uz, night, sign, warm, k in MELT_WANTS:
+        pts = s.uz_id == int(np.nonzero(s.uz_vals == f32(uz))[0][0])
+        steps = s.night == night
+        ks = int(np.nonzero(steps)[0][0])
+        blk = stratum_block(ref["E_in"], steps, pts)
+        sv = scale_floor(blk[np.isfinite(blk)])
+        e = ref["E_in"][ks]
+        with np.errstate(invalid="ignore"):
+            cand = np.nonzero(pts & np.isfinite(e) & (np.abs(e) >= sv) & (np.sign(e) == sign) & ((s.pts["T_air"] > 0) == warm))[0]
+        assert len(cand), (uz, night, sign, warm)
+        i = int(rng.choice(cand))
+        idx.append(i), step.append(ks), kind.append(k), floor.append(sv), e_ref.append(e[i])
+    return SimpleNamespace(idx=np.array(idx), step=np.array(step), kind=np.array(kind), floor=np.array(floor),
+                           e_ref=np.array(e_ref))
+
+
+def snowfall_cold(cfg, P_snow, T_air, RH):
+    """The snowfall's cold content as tfg_oracle.py:531-543 forms it (same operations, same order)."""
+    c = _cfgc(cfg)
+    with np.errstate(all="ignore"):
+        new_h_snow = (P_snow * c["dt"]) * (np.float64(c["rho_H2O"]) / np.float64(c["rho_snow"]))
+        T_wb = (T_air * np.arctan(0.151977 * ((RH + 8.313659) ** 0.5)) + np.arctan(T_air + RH) - np.arctan(RH - 1.676331)
+                + ((0.00391838 * (RH**1.5)) * np.arctan(0.023101 * RH)) - 4.86035)
+        del_T = np.float64(c["T0"]) - T_wb
+        return np.where(P_snow > 0, (np.float64(c["rho_snow"]) * np.float64(c["Cp_snow"])) * new_h_snow * del_T, 0.0)
+
+
+def melt_oracle(case, st):
+    """One OracleGrid.step of every cell of a melt case from the state `st` (h_swe, h_iwe, Eccs, Ecci; the
+    depths follow): the step's result, with E_in, cold, P_snow, P_rain, vol_SM and vol_IM (the cell's terms
+    of the two integrals) added."""
+    c, p = _cfgc(case.cfg), case.pts
+    ws, wi = np.float64(c["rho_H2O"]) / np.float64(c["rho_snow"]), np.float64(c["rho_H2O"]) / np.float64(c["rho_ice"])
+    m = O.OracleGrid(dict(case.cfg, SATTERLUND=case.sat), elev=p["elev"], slope=p["slope"], aspect=p["aspect"],
+                     h0_snow=st["h_swe"] * ws, h0_ice=st["h_iwe"] * wi, h0_swe=st["h_swe"], h0_iwe=st["h_iwe"])
+    m.n, m.albedo = p["n"].copy(), p["albedo"].copy()
+    m.Eccs, m.Ecci = np.array(st["Eccs"], np.float64), np.array(st["Ecci"], np.float64)
+    return m, _oracle_step(case, m)
+
+
+def _oracle_step(case, m):
+    p = case.pts
+    with np.errstate(all="ignore"):
+        m.cell_vol_SM = m.cell_vol_IM = np.float64(0.0)  # this step's terms alone (the sums are the test's)
+        r = dict(m.step(*(p[v] for v in FORCING), case.jd_cell, case.th_cell))
+    r["E_in"] = r["Q_sum"] * m.dt
+    T_rs = np.float64(m.c["T_rain_snow"])
+    r["P_snow"], r["P_rain"] = p["P"] * (p["T_air"] <= T_rs), p["P"] * (p["T_air"] > T_rs)
+    r["cold"] = snowfall_cold(case.cfg, r["P_snow"], p["T_air"], r["RH"])
+    r["vol_SM"], r["vol_IM"] = m.cell_vol_SM, m.cell_vol_IM
+    return {k: np.array(v, copy=True) for k, v in r.items() if np.ndim(v) == 1}  # the per-cell results
+
+
+def melt_tail(cfg, E_in, cold, P_snow, P_rain, st, variant: str):
+    """The step's tail alone, fp64 numpy: from E_in, the snowfall's cold content and the state (h_swe, h_iwe,
+    Eccs, Ecci, h_ice: the depth before the step) to MELT_TAIL_OUT, plus the gate quantities ("gates").
+
+    "reference"  tfg_oracle.py:511-571 line by line.
+    "fast"       melt_core / melt_fast of the fp32 engine (tfg_physics.hpp): SM 3600 = E_rem c_sm3600 with
+                 c_sm3600 = 3600 / (dt rho_H2O Lf); IM = E_rem inv_dt_rhoLf; the cap h_iwe inv_dt; t (1/3600.)
+                 for t / 3600; dt3600 = dt 3600 folded into one factor; the SM integral from the fp32 E_rem
+                 with the folded factor, the IM integral from the fp32 IM; SM, IM rounded to fp32 and M_total
+                 summed in fp32, as the history holds them (h_snow, h_ice stay fp64: the state's)."""
+    c = _cfgc(cfg)
+    dt = np.float64(c["dt"])
+    rho_H2O, Lf = np.float64(c["rho_H2O"]), np.float64(c["Lf"])
+    ws, wi = rho_H2O / np.float64(c["rho_snow"]), rho_H2O / np.float64(c["rho_ice"])
+    da_m2 = c["da"] * 1e6
+    zero = np.float64(0)
+    h_swe0, h_iwe0, Eccs0, Ecci0, h_ice0 = (np.asarray(st[k], np.float64) for k in ("h_swe", "h_iwe", "Eccs", "Ecci", "h_ice"))
+    E_in, cold, P_snow, P_rain = (np.asarray(a, np.float64) for a in (E_in, cold, P_snow, P_rain))
+    previous_swe = h_swe0
+    E_rem_s = np.maximum(E_in - Eccs0, zero)
+    E_rem_i = np.maximum(E_in - Ecci0, zero)
+    avail = h_swe0 + P_snow * dt
+    if variant == "reference":
+        SM = (E_rem_s / dt) / (rho_H2O * Lf)
+        SM = np.maximum(SM, zero)
+        vol_SM = SM * da_m2 * dt * 3600
+        sm3600 = SM * 3600
+        t = np.minimum(sm3600, avail)
+        SM = t / 3600
+        h_swe = np.maximum(avail - SM * dt * 3600, zero)
+        IM = np.maximum((E_rem_i / dt) / (rho_H2O * Lf), zero)
+        IM = np.where((h_swe == 0) & (previous_swe == 0), IM, zero)
+        im_gated = IM
+        IM = np.maximum(np.minimum(IM, h_iwe0 / dt), zero)
+        vol_IM = IM * da_m2 * dt * 3600
+        im3600 = IM * 3600
+        t = np.minimum(im3600, h_iwe0)
+        IM = t / 3600
+        h_iwe = np.maximum(h_iwe0 - IM * dt * 3600, zero)
+        M_total = IM + SM + P_rain / 3600
+    elif variant == "fast":
+        c_sm3600, inv_dt_rhoLf = 3600.0 / (dt * (rho_H2O * Lf)), 1.0 / (dt * (rho_H2O * Lf))
+        inv_dt, dt3600, inv3600 = 1.0 / dt, dt * 3600.0, 1.0 / 3600.0
+        vol_SM = E_rem_s.astype(np.float32).astype(np.float64) * (inv_dt_rhoLf * da_m2 * dt * 3600.0)
+        sm3600 = E_rem_s * c_sm3600
+        SM = np.minimum(sm3600, avail) * inv3600
+        h_swe = np.maximum(avail - SM * dt3600, zero)
+        IM = np.where((h_swe == 0) & (previous_swe == 0), E_rem_i * inv_dt_rhoLf, zero)
+        im_gated = IM
+        IM = np.minimum(IM, h_iwe0 * inv_dt)
+        vol_IM = IM.astype(np.float32).astype(np.float64) * (da_m2 * dt * 3600.0)
+        im3600 = IM * 3600.0
+        IM = np.minimum(im3600, h_iwe0) * inv3600
+        h_iwe = np.maximum(h_iwe0 - IM * dt3600, zero)
+        SM, IM = SM.astype(np.float32), IM.astype(np.float32)
+        M_total = (IM + SM + P_rain.astype(np.float32) * (np.float32(1.0) / np.float32(3600.0))).astype(np.float64)
+        SM, IM = SM.astype(np.float64), IM.astype(np.float64)
+    else:
+        raise ValueError(variant)
+    Eccs = np.where(P_snow > 0, np.maximum((Eccs0 + cold) - E_in, zero), Eccs0)
+    Ecci = np.where(h_ice0 == 0, zero, np.maximum(Ecci0 - E_in, zero))
+    h_snow, h_ice = h_swe * ws, h_iwe * wi
+    Eccs = np.where(P_snow <= 0, np.maximum(Eccs - E_in, zero), Eccs)
+    Eccs = np.where(h_snow == 0, zero, Eccs)
+    out = dict(SM=SM, IM=IM, M_total=M_total, h_swe=h_swe, h_iwe=h_iwe, Eccs=Eccs, Ecci=Ecci, h_snow=h_snow, h_ice=h_ice,
+               vol_SM=vol_SM, vol_IM=vol_IM)
+    out["gates"] = dict(E_rem_s=E_rem_s, E_rem_i=E_rem_i, avail=avail, sm3600=sm3600, im_gated=im_gated, im3600=im3600,
+                        capped=(sm3600 >= avail) & (avail > 0))
+    return out
+
+
+def melt_decisions(o, capped=None):
+    """The tail's decisions as they show in its results: which of SM, IM, Eccs, Ecci, h_swe, h_iwe are zero,
+    and `capped` (SM 3600 == the snow available, avail > 0: given, or from the restatement's gates)."""
+    d = {f"{k}==0": np.asarray(o[k]) == 0 for k in ("SM", "IM", "Eccs", "Ecci", "h_swe", "h_iwe")}
+    d["capped"] = np.asarray(o["gates"]["capped"] if capped is None else capped)
+    return d
+
+
+def melt_margins(case, ref, st):
+    """Per gate of the tail, [cells]: the oracle's distance from the threshold in energy-equivalent units,
+    divided by S; inf where the gate is not reached (its outcome is fixed by gates before it) or where both
+    sides are exactly zero (both outcomes give the same result).  A cell is decidable when all are >=
+    MELT_MARGIN.  Gates: E - Eccs0 and E - Ecci0 (the melt gates; without snowfall also Eccs's survival);
+    G - Eccs0 (Eccs's survival under snowfall); SM 3600 against the snow available (the cap) and SM 3600 dt
+    against it (melt-out when not capped); IM against h_iwe / dt, IM 3600 against h_iwe, IM 3600 dt against
+    h_iwe, where the ice gate is open."""
+    c = melt_c(case.cfg)
+    dt = np.float64(case.cfg["dt"])
+    t = melt_tail(case.cfg, ref["E_in"], ref["cold"], ref["P_snow"], ref["P_rain"], dict(st, h_ice=st["h_iwe"]), "reference")
+    g = t["gates"]
+    S = case.S(ref)
+    inf = np.full(case.n, np.inf)
+
+    def dist(a, b, live):
+        d = np.abs(np.asarray(a) - np.asarray(b))
+        return np.where(live & ~((np.asarray(a) == 0) & (np.asarray(b) == 0)), d / S, inf)
+
+    on = np.ones(case.n, bool)
+    snowing = ref["P_snow"] > 0
+    m_s, m_i = g["sm3600"], g["im_gated"] * 3600
+    ice_open = g["im_gated"] > 0
+    return {"E-Eccs0": dist(ref["E_in"], st["Eccs"], on),
+            "E-Ecci0": dist(ref["E_in"], st["Ecci"], on),
+            "G-Eccs0": dist(ref["E_in"] - ref["cold"], st["Eccs"], snowing),
+            "cap": dist(m_s / c, g["avail"] / c, m_s > 0),
+            "melt-out": dist(m_s * dt / c, g["avail"] / c, (m_s > 0) & (m_s < g["avail"])),
+            "ice rate cap": dist(m_i / c, st["h_iwe"] * 3600 / dt / c, ice_open),  # IM = m_i / 3600 against h_iwe / dt
+            "ice cap": dist(m_i / c, st["h_iwe"] / c, ice_open),
+            "ice melt-out": dist(m_i * dt / c, st["h_iwe"] / c, ice_open & (m_i < st["h_iwe"]))}
+
+
+def _melt_states(case, E, cold):
+    """The state grid from (E, cold) per cell: the comment at the head of this section."""
+    a, b, sw, iw = case.ax
+    dt, c = np.float64(case.cfg["dt"]), melt_c(case.cfg)
+    S = np.maximum(np.maximum(np.abs(E), np.abs(cold)), case.floor)
+    G = np.abs(np.where(case.snowing, E - cold, E))
+    Ea = np.abs(E)
+
+    def five(q, k):
+        off = MELT_OFF * np.maximum(q, S)
+        return np.maximum(np.choose(k, [0.0 * q, q / 2, q - off, q + off, 2 * q]), 0.0)
+
+    Eccs0, Ecci0 = five(G, a), five(Ea, b)
+    m_s, m_i = np.maximum(E - Eccs0, 0.0) * c, np.maximum(E - Ecci0, 0.0) * c
+    # 0.6 S for the depths: where Eccs0 = G - MELT_OFF S (m = MELT_OFF S c), m +- MELT_OFF S c would be 0 and 2 m, the
+    # melt-out threshold at dt = 2; m (1 +- 0.6) is MELT_MARGIN S c or more from m, 2 m and m / 4
+    off_s, off_i = MELT_OFF * np.maximum(m_s, 0.6 * S * c), MELT_OFF * np.maximum(m_i, 0.6 * S * c) * dt
+    fall = np.where(case.snowing, case.pts["P"] * dt, 0.0)
+    # what is available after the snowfall: h_swe0 = target - P_snow dt (0 where the snowfall alone exceeds it)
+    target = np.choose(sw, [0.0 * m_s, 0.0 * m_s, m_s / 2, m_s - off_s, m_s + off_s, 10 * m_s + 1])
+    h_swe0 = np.where(sw == 0, 0.0, np.where(sw == 1, 1e-12, np.maximum(target - fall, 0.0)))
+    # h_iwe0: none; half of what the rate cap IM <= h_iwe / dt admits (IM = m_i / 3600: the cap binds); the
+    # melt-out threshold m_i dt: 0.4 of it (half of it is the cap min(IM 3600, h_iwe)'s own threshold at dt = 2:
+    # a tie), just below and just above it; plenty
+    h_iwe0 = np.maximum(np.choose(iw, [0.0 * m_i, m_i * dt / 7200, 0.4 * m_i * dt, m_i * dt - off_i, m_i * dt + off_i, 10 * m_i + 1]), 0.0)
+    return dict(h_swe=h_swe0, h_iwe=h_iwe0, Eccs=Eccs0, Ecci=Ecci0)
+
+
+@lru_cache(maxsize=None)
+def melt_case(satterlund: bool, dt: float):
+    """The melt-state case of one (vapour-pressure form, dt): every point of melt_points() crossed with the
+    state grid.  pts: per cell, as a sweep's (the state's depths, n, albedo and window included, so that
+    gpu_probe and gpu_probe_one_cell inject them); st: the injected h_swe, h_iwe, Eccs, Ecci; ref: the
+    oracle's step from that state (melt_oracle); jd, th: the sweep's two clock steps, step_cell the one each
+    cell is compared at.  The grid is placed from the oracle's E_in and cold at the cell's OWN state (both
+    read the depths and the albedo), found by iterating state -> oracle -> state until E_in moves by no more
+    than 1e-13 S (`residual`: the last round's largest move; the host test asserts it); `ref` is the oracle
+    at the final state, and melt_margins() of it is what the host test asserts."""
+    s, mp = get_sweep("A", satterlund), melt_points(satterlund)
+    NP = len(mp.idx)
+    ix = np.indices((NP,) + MELT_AXES).reshape(5, -1)
+    pnt, ax = ix[0], tuple(ix[1:])
+    src = mp.idx[pnt]
+    pts = {k: np.ascontiguousarray(s.pts[k][src]) for k in FORCING + ("elev", "slope", "aspect", "n", "albedo", "ring")}
+    pts["P"] = np.where(mp.kind[pnt] == DRY, 0.0, MELT_P)
+    cfg = dict(s.cfg, dt=dt)
+    case = SimpleNamespace(name=f"melt-dt{dt:g}", cfg=cfg, sat=bool(satterlund), pts=pts, n=len(pnt), point=pnt, ax=ax,
+                           jd=s.jd, th=s.th, night=s.night, step_cell=mp.step[pnt], jd_cell=s.jd[mp.step[pnt]],
+                           th_cell=s.th[mp.step[pnt]], kind=mp.kind[pnt], floor=mp.floor[pnt] * dt, n_points=NP)
+    case.snowing = (pts["P"] > 0) & (pts["T_air"] <= _cfgc(cfg)["T_rain_snow"])
+    case.S = lambda ref: np.maximum(np.maximum(np.abs(ref["E_in"]), np.abs(ref["cold"])), case.floor)
+    # first guess: the oracle's E_in over 1 m of snow on ice (the sweep's own depths reach the mast's top)
+    z = np.zeros(case.n)
+    _, ref = melt_oracle(case, dict(h_swe=z + 0.3, h_iwe=z + 2.0, Eccs=z, Ecci=z))
+    E, cold = ref["E_in"], ref["cold"]
+    for _ in range(24):  # the windy points' E_in reads the snow depth through the roughness: a dozen rounds
+        st = _melt_states(case, E, cold)
+        _, ref = melt_oracle(case, st)
+        case.residual = float(np.max(np.abs(ref["E_in"] - E) / case.S(ref)))  # of the last round, over S
+        E, cold = ref["E_in"], ref["cold"]
+        if case.residual <= 1e-13:
+            break
+    # A capped reservoir leaves h - fl(h / 3600) dt 3600: at dt = 1 zero or a last-place residual, decided by
+    # h's last bits, and not alike by h / 3600 and h (1/3600.) (the melt-out sweep measures how often).  Such
+    # cells are the sweep's business: a depth whose residual the two arithmetics decide differently is moved
+    # to the next fp64 number until they agree (both are functions of the depth alone there).
+    case.moved = 0
+    for _ in range(16):
+        t = [melt_tail(cfg, ref["E_in"], ref["cold"], ref["P_snow"], ref["P_rain"], dict(st, h_ice=st["h_iwe"]), v)
+             for v in ("reference", "fast")]
+        bad = [(t[0][k] == 0) != (t[1][k] == 0) for k in ("h_swe", "h_iwe")]
+        if not (bad[0].any() or bad[1].any()):
+            break
+        case.moved += int(bad[0].sum() + bad[1].sum())
+        for k, b in zip(("h_swe", "h_iwe"), bad):
+            st[k] = np.where(b, np.nextafter(st[k], np.inf), st[k])
+        _, ref = melt_oracle(case, st)
+    return _melt_finish(case, st, ref)
+
+
+def _melt_finish(case, st, ref):
+    c = _cfgc(case.cfg)
+    ws, wi = np.float64(c["rho_H2O"]) / np.float64(c["rho_snow"]), np.float64(c["rho_H2O"]) / np.float64(c["rho_ice"])
+    case.pts.update(h_swe=st["h_swe"], h_iwe=st["h_iwe"], h_snow=st["h_swe"] * ws, h_ice=st["h_iwe"] * wi)
+    case.st = dict(st, h_ice=case.pts["h_ice"])
+    case.ref = ref
+    for a in list(case.pts.values()) + list(case.st.values()) + list(ref.values()):
+        a.setflags(write=False)
+    return case
+
+
+@lru_cache(maxsize=None)
+def meltout_case(satterlund: bool, dt: float, ice: bool):
+    """The melt-out residual sweep of one dt: SWEEP_N seeded depths, log-uniform in SWEEP_RANGE, at the
+    strongly melting dry point (the day point of 3 m/s in warm air), no cold content.  ice = False: h_swe0
+    swept over h_iwe0 = 2 m; ice = True: h_iwe0 swept on bare ice.  ref, ref2: the oracle's first and second
+    step (the second shows the ice gate: IM > 0 exactly where the snow of the first left exactly zero)."""
+    s, mp = get_sweep("A", satterlund), melt_points(satterlund)
+    j = MELT_WANTS.index((3.0, False, 1, True, DRY))
+    src = np.full(SWEEP_N, mp.idx[j])
+    pts = {k: np.ascontiguousarray(s.pts[k][src]) for k in FORCING + ("elev", "slope", "aspect", "n", "albedo", "ring")}
+    pts["P"] = np.zeros(SWEEP_N)
+    rng = np.random.default_rng(SAMPLE_SEED + (1 if ice else 0))
+    h = np.exp(rng.uniform(np.log(SWEEP_RANGE[0]), np.log(SWEEP_RANGE[1]), SWEEP_N))
+    step = np.full(SWEEP_N, mp.step[j])
+    case = SimpleNamespace(name=f"meltout-{'ice' if ice else 'snow'}-dt{dt:g}", cfg=dict(s.cfg, dt=dt), sat=bool(satterlund),
+                           pts=pts, n=SWEEP_N, point=np.zeros(SWEEP_N, np.int64), jd=s.jd, th=s.th, night=s.night,
+                           step_cell=step, jd_cell=s.jd[step], th_cell=s.th[step], kind=np.full(SWEEP_N, DRY),
+                           floor=np.full(SWEEP_N, mp.floor[j] * dt), n_points=1)
+    case.snowing = np.zeros(SWEEP_N, bool)
+    case.S = lambda ref: np.maximum(np.abs(ref["E_in"]), case.floor)
+    z = np.zeros(SWEEP_N)
+    st = dict(h_swe=z if ice else h, h_iwe=h if ice else np.full(SWEEP_N, 2.0), Eccs=z.copy(), Ecci=z.copy())
+    m, ref = melt_oracle(case, st)
+    case.ref2 = _oracle_step(case, m)
+    return _melt_finish(case, st, ref)
+
+
+def meltout_steps(case, variant: str):
+    """Both steps of a melt-out case through melt_tail, each fed the oracle's E_in of that step."""
+    outs, st = [], case.st
+    for r in (case.ref, case.ref2):
+        t = melt_tail(case.cfg, r["E_in"], r["cold"], r["P_snow"], r["P_rain"], st, variant)
+        st = {k: t[k] for k in ("h_swe", "h_iwe", "Eccs", "Ecci", "h_ice")}
+        outs.append(t)
+    return outs
+
+
+@lru_cache(maxsize=None)
+def meltout_share(satterlund: bool, dt: float, ice: bool):
+    """Of the swept depths: the share left at exactly zero by the first step in each arithmetic, and the
+    share where the two disagree on it (a property of the two arithmetics, not of a kernel)."""
+    case, k = meltout_case(satterlund, dt, ice), "h_iwe" if ice else "h_swe"
+    a, b = meltout_steps(case, "reference")[0][k], meltout_steps(case, "fast")[0][k]
+    return {"zero_reference": float(np.mean(a == 0)), "zero_fast": float(np.mean(b == 0)),
+            "disagree": float(np.mean((a == 0) != (b == 0)))}
+
+
+def melt_classes(case):
+    """Per cell, the wave-uniform branches of the tail it takes: snowing | snow melts | ice melts | capped."""
+    r = case.ref
+    t = melt_tail(case.cfg, r["E_in"], r["cold"], r["P_snow"], r["P_rain"], case.st, "reference")
+    return (case.snowing.astype(int) + 2 * (r["SM"] > 0).astype(int) + 4 * (r["IM"] > 0).astype(int)
+            + 8 * t["gates"]["capped"].astype(int))
+
+
+def probe_ecc(E):
+    """The cold content K injected to read a cell's E_in back: the power of two with 4 |E| <= K < 8 |E|
+    (2^-20 where E is zero or not finite), so that nothing melts and K - E_in lies in (K / 2, 2 K).
+    Exactness for the fp32-flux forms: there E_in is an fp32 number, a multiple of 2^-24 |E_in| >= 2^-27 K
+    (|E_in| > K / 8), and fp64 numbers below 2 K are spaced 2^-52 K or finer, so K - E_in is
+    representable: the subtraction does not round."""
+    a = np.abs(np.asarray(E, np.float64))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(np.isfinite(a) & (a > 0), 2.0 ** np.ceil(np.log2(np.where(a > 0, 4 * a, 1.0))), 2.0 ** -20)
+
+
+def melt_probe_case(case):
+    """The case as the probe run steps it: the same cells, but every cell with snow and no ice stands on 2 m
+    of ice, so that its E_in reads from Ecci and, under snowfall, its cold content from Eccs beside it.
+    Under snow the step's energy terms read neither h_ice nor h_iwe (the surface clamp and the albedo ask
+    h_snow > 0 first), so such a cell forms the E_in and cold of the cell it stands for from the same
+    numbers.  readable: [cells] False for the cells with neither snow nor ice, whose cold contents the step
+    resets (under snowfall only E_in - cold survives, in Eccs): nothing can be read there."""
+    c = _cfgc(case.cfg)
+    wi = np.float64(c["rho_H2O"]) / np.float64(c["rho_ice"])
+    on_ice = (case.pts["h_ice"] == 0) & (case.pts["h_snow"] > 0)
+    sub = SimpleNamespace(**vars(case))
+    sub.pts = dict(case.pts, h_iwe=np.where(on_ice, 2.0, case.pts["h_iwe"]), h_ice=np.where(on_ice, 2.0 * wi, case.pts["h_ice"]))
+    sub.readable = sub.pts["h_ice"] > 0
+    return sub
