@@ -279,6 +279,48 @@ typedef struct tfg_forcing_grid {
 int tfg_set_gridded_forcing(tfg_handle* h, int frame0, int nframes, const double* src, int src_on_device,
                             const double* z_src, const tfg_forcing_grid* g, const tfg_downscale* ds);
 
+/* The catchment-id raster (TFG_ST_CATCH_ID) from polygons, filled on the
+ * device: cell (r, c) of this shard gets the id of the LAST polygon p, in table
+ * order, with r0 <= r < r1 and c0 <= c < c1 (its poly_box) whose shell (its
+ * first ring) contains the cell centre (px[c], py[r]) and none of whose other
+ * rings (holes) does; a cell in no polygon gets outside_id.  Containment is the
+ * even-odd crossing test: edge (a, b) -> (c, d) counts for the centre when
+ *   (b > py) != (d > py)  and  px < a + (py - b) * (c - a) / (d - b),
+ * the right side in fp64, left to right, each operation rounded once (no
+ * contraction), so the raster equals a numpy evaluation of the same rule bit
+ * for bit (hydrofabric.rasterize_divides; hydrofabric.polygon_tables builds
+ * the tables, centres and boxes from divides with that function's own
+ * expressions).  A polygon without rings covers nothing.  Row-block shards
+ * pass their own rows' py and boxes clipped to their rows: a shard's raster
+ * is the whole grid's rows.
+ * All pointers are host memory, borrowed for the call: the tables are copied
+ * into the pinned staging ring and the call is queued on the handle's stream;
+ * it waits for the device only when `cells` is given.  cells [n_catch]
+ * (or NULL) receives the number of cells of each id.  The raster is allocated
+ * on first use as by tfg_set_field(TFG_ST_CATCH_ID), and later launches take
+ * the per-catchment form; the ids are valid by construction, so nothing is
+ * read back.
+ * TFG_ERR_ARG (the handle and its raster stay as they were): null handle or
+ * p, a negative count, a null table that is needed, a poly_id or outside_id
+ * outside [0, n_catch), poly_ring0 or ring_edge0 not starting at 0, decreasing
+ * or ending past n_rings (ring_edge0: any end), a box outside
+ * 0 <= r0 <= r1 <= ny, 0 <= c0 <= c1 <= nx, a non-finite edge or centre, an edge
+ * with b == d.
+ * No reference counterpart (one cell per catchment); the rule is restated in
+ * numpy by tests/raster_ref.py. */
+typedef struct tfg_polygons {
+  int32_t        n_poly;     /* polygons, in the order that decides overlaps (last wins) */
+  const int32_t* poly_id;    /* [n_poly] id written for the polygon's cells, in [0, n_catch) */
+  const int32_t* poly_ring0; /* [n_poly + 1] first ring of each polygon; ring 0 of a polygon is its shell */
+  const int32_t* poly_box;   /* [n_poly][4] r0, r1, c0, c1: half-open cell box inside this shard */
+  int32_t        n_rings;
+  const int64_t* ring_edge0; /* [n_rings + 1] */
+  const double*  edges;      /* [n_edges][4] a, b, c, d; no edge with b == d */
+  const double*  px;         /* [nx] cell-centre x */
+  const double*  py;         /* [ny] cell-centre y of this shard's rows */
+} tfg_polygons;
+int tfg_rasterize_polygons(tfg_handle* h, const tfg_polygons* p, int outside_id, int64_t* cells /* [n_catch] host, or NULL */);
+
 /* The eight BMI outputs in _output_vars order (:28-37): h_snow, h_swe, SM,
  * h_ice, h_iwe, IM, M_total, RH, as dst[8][n], from output-history slot
  * `hist` (h_swe/h_iwe: the current state).  One gather and one copy.

@@ -501,6 +501,7 @@ __global__ void k_terrain(const R* __restrict__ elev, const double* __restrict__
 #include "tfg_aggregate.hpp"  // per-cell time aggregates of history planes (tfg_cell_aggregate)
 #include "tfg_forcing.hpp"  // forcing spread over the grid: per catchment (tfg_set_catchment_forcing), regridded (tfg_set_gridded_forcing)
 #include "tfg_coarse.hpp"  // per-node sums and counts of history planes on a coarse grid (tfg_coarse_series)
+#include "tfg_raster.hpp"  // polygons filled into the catchment-id raster (tfg_rasterize_polygons)
 
 // tfg_set_inputs / tfg_get_outputs: the per-step BMI traffic of one call each.
 // src [5][n]: P_air, Hum_sp, P, T_air, uz (BMI order) -> frame planes.
@@ -2424,6 +2425,87 @@ int tfg_set_gridded_forcing(tfg_handle* h, int frame0, int nframes, const double
     HIPCHK(h, hipGetLastError());
   }
   if (s) HIPCHK(h, StageRing::commit(*s, h->stream));
+  return TFG_OK;
+}
+
+int tfg_rasterize_polygons(tfg_handle* h, const tfg_polygons* p, int outside_id, int64_t* cells) {
+  if (int rc_ = api_sync(h)) return rc_;  // after a split launch's second part
+  if (!h) return fail(nullptr, TFG_ERR_ARG, "null handle");
+  if (!p) return fail(h, TFG_ERR_ARG, "rasterize: null polygons");
+  if (p->n_poly < 0 || p->n_rings < 0) return fail(h, TFG_ERR_ARG, "rasterize: n_poly and n_rings must be >= 0");
+  if (!p->px || !p->py) return fail(h, TFG_ERR_ARG, "rasterize: null px or py");
+  if (!p->poly_ring0 || !p->ring_edge0 || (p->n_poly && (!p->poly_id || !p->poly_box)))
+    return fail(h, TFG_ERR_ARG, "rasterize: null table");
+  if (outside_id < 0 || outside_id >= h->n_catch) return fail(h, TFG_ERR_ARG, "rasterize: outside_id out of [0, n_catch)");
+  if (h->n_catch > kRasterMaxCatch) return fail(h, TFG_ERR_ARG, "rasterize: n_catch > 512 not supported");
+  const int64_t tiles = (h->nx + kRasterTile - 1) / kRasterTile;
+  if (h->nx > INT32_MAX || h->ny > INT32_MAX || h->ny * tiles > INT32_MAX)
+    return fail(h, TFG_ERR_ARG, "rasterize: grid too large (ny * ceil(nx / 1024) must be < 2^31)");
+  // everything the kernel indexes with is checked here, before anything is queued or allocated
+  if (p->poly_ring0[0] != 0 || p->ring_edge0[0] != 0) return fail(h, TFG_ERR_ARG, "rasterize: offsets must start at 0");
+  for (int32_t i = 0; i < p->n_poly; ++i) {
+    if (p->poly_id[i] < 0 || p->poly_id[i] >= h->n_catch) return fail(h, TFG_ERR_ARG, "rasterize: polygon id out of [0, n_catch)");
+    if (p->poly_ring0[i + 1] < p->poly_ring0[i]) return fail(h, TFG_ERR_ARG, "rasterize: poly_ring0 decreases");
+    const int32_t* b = p->poly_box + 4 * (size_t)i;
+    if (b[0] < 0 || b[1] < b[0] || b[1] > h->ny || b[2] < 0 || b[3] < b[2] || b[3] > h->nx)
+      return fail(h, TFG_ERR_ARG, "rasterize: polygon box outside the grid");
+  }
+  if (p->poly_ring0[p->n_poly] > p->n_rings) return fail(h, TFG_ERR_ARG, "rasterize: poly_ring0 ends past n_rings");
+  for (int32_t k = 0; k < p->n_rings; ++k)
+    if (p->ring_edge0[k + 1] < p->ring_edge0[k]) return fail(h, TFG_ERR_ARG, "rasterize: ring_edge0 decreases");
+  const int64_t n_edges = p->ring_edge0[p->n_rings];
+  if (n_edges && !p->edges) return fail(h, TFG_ERR_ARG, "rasterize: null edges");
+  for (int64_t e = 0; e < n_edges; ++e) {
+    const double* q = p->edges + 4 * e;
+    if (!std::isfinite(q[0]) || !std::isfinite(q[1]) || !std::isfinite(q[2]) || !std::isfinite(q[3]))
+      return fail(h, TFG_ERR_ARG, "rasterize: non-finite edge");
+    if (q[1] == q[3]) return fail(h, TFG_ERR_ARG, "rasterize: horizontal edge (b == d)");
+  }
+  for (int64_t i = 0; i < h->nx; ++i)
+    if (!std::isfinite(p->px[i])) return fail(h, TFG_ERR_ARG, "rasterize: non-finite cell centre");
+  for (int64_t i = 0; i < h->ny; ++i)
+    if (!std::isfinite(p->py[i])) return fail(h, TFG_ERR_ARG, "rasterize: non-finite cell centre");
+  HIPCHK(h, hipSetDevice(h->device));
+  // the tables, borrowed for this call only: one block through the staging ring, one queued copy;
+  // widest elements first, so every table starts aligned to its element
+  const size_t b_edges = (size_t)n_edges * 32, b_px = (size_t)h->nx * 8, b_py = (size_t)h->ny * 8,
+               b_re = ((size_t)p->n_rings + 1) * 8, b_box = (size_t)p->n_poly * 16, b_id = (size_t)p->n_poly * 4,
+               b_pr = ((size_t)p->n_poly + 1) * 4;
+  const size_t o_box = b_edges, o_px = o_box + b_box, o_py = o_px + b_px, o_re = o_py + b_py, o_id = o_re + b_re,
+               o_pr = o_id + b_id, bytes = o_pr + b_pr;
+  StageRing::Slot* s = nullptr;
+  HIPCHK(h, h->in_ring.acquire(bytes, true, &s));
+  char* hp = static_cast<char*>(s->host.ptr);
+  const char* dp = static_cast<const char*>(s->dev.ptr);
+  if (b_edges) std::memcpy(hp, p->edges, b_edges);
+  if (b_box) std::memcpy(hp + o_box, p->poly_box, b_box);
+  std::memcpy(hp + o_px, p->px, b_px);
+  std::memcpy(hp + o_py, p->py, b_py);
+  std::memcpy(hp + o_re, p->ring_edge0, b_re);
+  if (b_id) std::memcpy(hp + o_id, p->poly_id, b_id);
+  std::memcpy(hp + o_pr, p->poly_ring0, b_pr);
+  if (cells) HIPCHK(h, reserve_idle(h, h->rd_out_int, (size_t)h->n_catch * 8));
+  if (int rc = reserve_zeroed(h, h->catch_id, (size_t)h->n_pad * 4)) return rc;
+  HIPCHK(h, hipMemcpyAsync(s->dev.ptr, s->host.ptr, bytes, hipMemcpyHostToDevice, h->stream));
+  if (cells) HIPCHK(h, hipMemsetAsync(h->rd_out_int, 0, (size_t)h->n_catch * 8, h->stream));
+  RasterTables t;
+  t.edges = reinterpret_cast<const double2*>(dp);
+  t.poly_box = reinterpret_cast<const int4*>(dp + o_box);
+  t.px = reinterpret_cast<const double*>(dp + o_px);
+  t.py = reinterpret_cast<const double*>(dp + o_py);
+  t.ring_edge0 = reinterpret_cast<const int64_t*>(dp + o_re);
+  t.poly_id = reinterpret_cast<const int32_t*>(dp + o_id);
+  t.poly_ring0 = reinterpret_cast<const int32_t*>(dp + o_pr);
+  t.n_poly = p->n_poly;
+  hipLaunchKernelGGL(k_rasterize, (unsigned)(h->ny * tiles), kBlock, 0, h->stream, (int32_t*)h->catch_id, (int32_t)h->ny,
+                     (int32_t)h->nx, (int32_t)tiles, t, (int32_t)outside_id, (int32_t)h->n_catch,
+                     cells ? reinterpret_cast<unsigned long long*>((int64_t*)h->rd_out_int) : nullptr);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, StageRing::commit(*s, h->stream));
+  if (cells) {
+    HIPCHK(h, hipMemcpyAsync(cells, h->rd_out_int, (size_t)h->n_catch * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+  }
   return TFG_OK;
 }
 

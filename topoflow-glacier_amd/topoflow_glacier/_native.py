@@ -82,6 +82,13 @@ class TfgCellStats(ctypes.Structure):
                 ("count", ctypes.c_void_p), ("threshold", ctypes.c_double)]
 
 
+class TfgPolygons(ctypes.Structure):
+    """tfg_polygons: the flat tables of tfg_rasterize_polygons (host arrays; hydrofabric.polygon_tables)."""
+    _fields_ = [("n_poly", ctypes.c_int32), ("poly_id", ctypes.c_void_p), ("poly_ring0", ctypes.c_void_p),
+                ("poly_box", ctypes.c_void_p), ("n_rings", ctypes.c_int32), ("ring_edge0", ctypes.c_void_p),
+                ("edges", ctypes.c_void_p), ("px", ctypes.c_void_p), ("py", ctypes.c_void_p)]
+
+
 # tfg_uniforms, one record per time step (numpy structured dtype, C layout)
 _U_D = ["th", "omega_th", "cos_wth", "sin_wth", "sin_d", "cos_d", "tan_d", "isc_e0", "m_opt",
         "k_et_flat", "flat_sr", "flat_ss"]
@@ -151,6 +158,7 @@ def load() -> ctypes.CDLL:
         "tfg_set_catchment_forcing": ([vp, i32, i32, vp, i32, vp, ctypes.POINTER(TfgDownscale)], i32),
         "tfg_set_gridded_forcing": ([vp, i32, i32, vp, i32, vp, ctypes.POINTER(TfgForcingGrid),
                                      ctypes.POINTER(TfgDownscale)], i32),
+        "tfg_rasterize_polygons": ([vp, ctypes.POINTER(TfgPolygons), i32, vp], i32),
         "tfg_get_outputs": ([vp, i32, vp, i32, i64, i32], i32),
         "tfg_update": ([vp, i32, vp, i32, vp, vp, i32, i64], i32),
         "tfg_update_many": ([vp, i32, vp, vp, vp], i32),
@@ -335,5 +343,5 @@ def exported_symbols() -> list[str]:
         "tfg_update", "tfg_update_many", "tfg_conduction_edges", "tfg_conduction_update", "tfg_conduction_off",
         "tfg_nan_safe_launches", "tfg_set_step_form", "tfg_set_flux", "tfg_set_split", "tfg_join", "tfg_get_split",
         "tfg_selftest_powers", "tfg_catchment_series", "tfg_set_catchment_forcing", "tfg_cell_aggregate",
-        "tfg_set_gridded_forcing", "tfg_band_series", "tfg_coarse_series",
+        "tfg_set_gridded_forcing", "tfg_band_series", "tfg_coarse_series", "tfg_rasterize_polygons",
     ) if hasattr(L, n)]

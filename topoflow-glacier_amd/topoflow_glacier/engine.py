@@ -359,6 +359,38 @@ class GlacierEngine:
         self._chk(self.lib.tfg_set_gridded_forcing(self.h, int(frame0), int(a.shape[0]),
                                                    a.ctypes.data_as(ctypes.c_void_p), 0, zp, ctypes.byref(g), dsp))
 
+    def rasterize_divides(self, divides, x0: float, y0: float, cell: float, *, row0: int = 0,
+                          ny_global: int | None = None, outside_id: int | None = None, counts: bool = True):
+        """The catchment-id raster from hydrofabric divides, filled on the
+        device (tfg_rasterize_polygons): cell by cell what
+        hydrofabric.rasterize_divides and catchment_ids give on the host --
+        divide k -> id k, the last divide that covers a cell wins, cells in no
+        divide get `outside_id` (default len(divides)) -- for this shard's
+        rows row0 .. row0+ny-1 of a grid of ny_global rows (default: the
+        shard is the whole grid).  Needs n_catch > every id.  Only the
+        polygons' tables travel to the device; the raster is never on the host.
+
+        With `counts` (the default) returns the cells of each id, int64
+        [n_catch], and fills catchment_cells()' cache with them; the call then
+        waits for the device.  Without, returns None and is only queued."""
+        from . import hydrofabric
+
+        outside_id = len(divides) if outside_id is None else int(outside_id)
+        if ny_global is None:
+            ny_global = int(row0) + self.ny
+        if max(outside_id, len(divides) - 1) >= self.n_catch or outside_id < 0:
+            raise ValueError(f"ids 0 .. {len(divides) - 1} and outside_id {outside_id} need n_catch > them, not {self.n_catch}")
+        t = hydrofabric.polygon_tables(divides, x0, y0, cell, int(ny_global), self.nx, int(row0), self.ny)
+        ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+        p = nat.TfgPolygons(len(t.poly_id), ptr(t.poly_id), ptr(t.poly_ring0), ptr(t.poly_box), len(t.ring_edge0) - 1,
+                            ptr(t.ring_edge0), ptr(t.edges), ptr(t.px), ptr(t.py))
+        cells = np.zeros(self.n_catch, dtype=np.int64) if counts else None
+        self._chk(self.lib.tfg_rasterize_polygons(self.h, ctypes.byref(p), outside_id, ptr(cells) if counts else None))
+        self._catch_cells = cells  # None: catchment_cells() counts the new raster
+        self._catch_elev = None  # catchment_mean_elevation() sums the new raster
+        self._hypsometry = None  # hypsometry() counts the new rasters
+        return cells
+
     def catchment_mean_elevation(self):
         """(sum [n_catch], cells [n_catch]) of this shard: per catchment, the
         sum of the elevation raster as the engine holds it (fp32-rounded in

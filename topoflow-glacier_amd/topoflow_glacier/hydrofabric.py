@@ -28,7 +28,7 @@ from pathlib import Path
 import numpy as np
 
 __all__ = ["Divide", "read_divides", "load_divides_npz", "parse_gpkg_geometry", "ring_area", "grid_covering",
-           "rasterize_divides", "catchment_ids"]
+           "rasterize_divides", "catchment_ids", "PolygonTables", "polygon_tables"]
 
 
 @dataclass
@@ -156,6 +156,65 @@ def rasterize_divides(divides: list, x0: float, y0: float, cell: float, ny: int,
             sub = ids[r0:r1, c0:c1]
             sub[m] = k
     return ids
+
+
+@dataclass
+class PolygonTables:
+    """The flat tables of tfg_rasterize_polygons (include/tfg.h tfg_polygons) for one shard."""
+    poly_id: np.ndarray     # int32 [n_poly] divide index of each polygon
+    poly_ring0: np.ndarray  # int32 [n_poly + 1] first ring of each polygon; its ring 0 is the shell
+    poly_box: np.ndarray    # int32 [n_poly][4] r0, r1, c0, c1 in the shard's rows
+    ring_edge0: np.ndarray  # int64 [n_rings + 1]
+    edges: np.ndarray       # float64 [n_edges][4] a, b, c, d, without horizontal edges
+    px: np.ndarray          # float64 [nx]
+    py: np.ndarray          # float64 [rows]
+
+
+def polygon_tables(divides: list, x0: float, y0: float, cell: float, ny: int, nx: int, row0: int = 0,
+                   rows: int | None = None) -> PolygonTables:
+    """`divides` as the tables the device fill reads (GlacierEngine.rasterize_divides), for rows
+    row0 .. row0+rows-1 (default: to the end) of the ny x nx grid of rasterize_divides.  The cell
+    centres and each polygon's cell box are rasterize_divides' own expressions on the global row
+    and column index, the box then clipped to the shard; a polygon whose box misses the shard is
+    dropped, as are horizontal edges (_inside skips them).  Divides without polygons are allowed.
+    A non-finite vertex raises ValueError."""
+    rows = ny - row0 if rows is None else int(rows)
+    if row0 < 0 or rows < 0 or row0 + rows > ny:
+        raise ValueError(f"rows {row0} .. {row0 + rows} outside the grid's {ny}")
+    px = x0 + (np.arange(0, nx) + 0.5) * cell
+    py = y0 - (np.arange(row0, row0 + rows) + 0.5) * cell
+    poly_id, poly_ring0, poly_box, ring_edge0, edges = [], [0], [], [0], []
+    n_edges = 0
+    for k, d in enumerate(divides):
+        for poly in d.polygons:
+            rings = [np.asarray(r, dtype=np.float64).reshape(-1, 2) for r in poly]
+            if not all(np.isfinite(r).all() for r in rings):
+                raise ValueError(f"divide {k}: non-finite vertex")
+            if not rings or not len(rings[0]):
+                continue
+            sh = rings[0]
+            c0 = max(int(np.floor((sh[:, 0].min() - x0) / cell)), 0)
+            c1 = min(int(np.ceil((sh[:, 0].max() - x0) / cell)) + 1, nx)
+            r0 = max(int(np.floor((y0 - sh[:, 1].max()) / cell)), 0)
+            r1 = min(int(np.ceil((y0 - sh[:, 1].min()) / cell)) + 1, ny)
+            if c0 >= c1 or r0 >= r1:
+                continue
+            r0, r1 = max(r0, row0), min(r1, row0 + rows)
+            if r0 >= r1:
+                continue
+            poly_id.append(k)
+            poly_box.append((r0 - row0, r1 - row0, c0, c1))
+            for ring in rings:
+                e = np.concatenate([ring, np.roll(ring, -1, axis=0)], axis=1)  # a, b, c, d
+                e = e[e[:, 1] != e[:, 3]]
+                edges.append(e)
+                n_edges += len(e)
+                ring_edge0.append(n_edges)
+            poly_ring0.append(len(ring_edge0) - 1)
+    return PolygonTables(
+        np.asarray(poly_id, dtype=np.int32), np.asarray(poly_ring0, dtype=np.int32),
+        np.asarray(poly_box, dtype=np.int32).reshape(-1, 4), np.asarray(ring_edge0, dtype=np.int64),
+        np.ascontiguousarray(np.concatenate(edges) if edges else np.zeros((0, 4))), px, py)
 
 
 def load_divides_npz(path: str | Path) -> tuple[int, list]:
