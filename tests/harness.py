@@ -321,6 +321,52 @@ def valid_mask(flip: np.ndarray, nsteps: int) -> np.ndarray:
     return (flip[None, :] < 0) | (k < flip[None, :])
 
 
+HIST_OUTPUTS = ("h_snow", "SM", "h_ice", "IM", "M_total", "RH")
+STATE_PLANES = ("h_swe", "h_iwe", "Eccs", "Ecci", "albedo", "n")
+
+
+def assert_oracle_rule(outs: dict, state: dict, ref: dict, ref_state, tol: float = 1e-5) -> SimpleNamespace:
+    """The suite's rule for a run with or without missing data, asserted: the
+    per-step outputs [nsteps][ncell] and the final state planes of an engine
+    against the numpy oracle's (`ref_state`: the OracleGrid, or a dict).  NaN
+    exactly where the oracle has NaN; no failure that melt_out_flips cannot
+    classify; the finite values of cells not yet flipped within the floored
+    `tol` (parity, the floor taken over the oracle's finite values).  Returns
+    the worst error per output and state plane and the flipped cells."""
+    nsteps = np.asarray(ref["M_total"]).shape[0]
+    flip, genuine = melt_out_flips(outs, ref, tol)
+    assert not genuine, genuine
+    ok_steps = valid_mask(flip, nsteps)
+    err = {}
+    for v in HIST_OUTPUTS:
+        np.testing.assert_array_equal(np.isnan(outs[v]), np.isnan(ref[v]), err_msg=v)
+        ok = ~np.isnan(ref[v]) & ok_steps
+        err[v] = parity(outs[v], np.where(np.isnan(ref[v]), 0.0, ref[v]), mask=ok)[0]
+        assert err[v] <= tol, (v, err[v])
+    for v in STATE_PLANES:
+        want = np.asarray(ref_state[v] if isinstance(ref_state, dict) else getattr(ref_state, v), np.float64)
+        np.testing.assert_array_equal(np.isnan(state[v]), np.isnan(want), err_msg=v)
+        err[v] = parity(state[v], want, mask=np.isfinite(want) & ok_steps[-1])[0]
+        assert err[v] <= tol, (v, err[v])
+    return SimpleNamespace(err=err, flip=flip, flips=int((flip >= 0).sum()))
+
+
+def read_run(eng, nsteps: int) -> SimpleNamespace:
+    """Everything a finished run of nsteps <= hist_depth steps left behind, as
+    host arrays: the six outputs of every step [nsteps][ncell], the state
+    planes, the fp64 previous-step depths the next step would read
+    (TFG_PREV_DEPTH), all snowfall-window slots [ring_len][ncell], the
+    diagnostics [n_catch][6] and the count of NaN-safe launches."""
+    from topoflow_glacier import _native as nat
+
+    eng.sync()
+    outs = {v: np.stack([eng.get_field(v, index=k) for k in range(nsteps)]) for v in HIST_OUTPUTS}
+    state = {v: eng.get_field(v) for v in STATE_PLANES}
+    window, diag, ns_launches = read_window(eng), eng.diagnostics(), eng.nan_safe_launches()
+    prev = {v: eng.get_field(v, index=nat.PREV_DEPTH) for v in ("h_snow", "h_ice")}  # last: it materialises the depths
+    return SimpleNamespace(outs=outs, state=state, prev=prev, window=window, diag=diag, ns_launches=ns_launches)
+
+
 def classify_sample(gpu: dict, ref: dict, c64: dict, cfg: dict, tol: float, onsets: bool) -> SimpleNamespace:
     """Every rule of a parity check on one sample, as the GPU suite, smoke and
     each bench rank apply them: depletion steps, melt-out flips (held to the

@@ -2,7 +2,9 @@
 (k_forcing_expand; tfg_set_catchment_forcing), through
 GlacierEngine.set_catchment_forcing and
 hydrograph.forced_catchment_hydrographs: the frames against the numpy
-restatement of the rule (tests/downscale_ref.py), the precipitation clamp,
+restatement of the rule (tests/downscale_ref.py) under both vapour-pressure
+formulas (the humidity cap's e_sat is the model's configured one), the
+precipitation clamp,
 batches and the frame range, several tiles per workgroup, split launches,
 missing data, the humidity cap end to end, the hydrograph against the numpy
 oracle, the rejected arguments, and the pinned staging ring it shares with
@@ -34,6 +36,9 @@ holds the same figures), the largest error of each kind:
   frames against the restatement, three maps, host and device tables
       fp32 5.8e-8 (uz, a pure conversion: one rounding to fp32 is 6.0e-8),
       fp64 9.4e-16 (Hum_sp; P_air 4.5e-16; T_air, P and uz exact)
+  the same with SATTERLUND: true (`divide`; the cap binds in 42.6 % of the
+      cell-frames and parts from Brutsaert's by up to 6.8e-3 relative there)
+      fp32 5.7e-8, fp64 8.4e-16 (both Hum_sp)
   with the clamp (grad_P = 2e-3)                       fp32 5.6e-8, fp64 9.4e-16
   1152 x 2048, 512 ids, against the restatement         fp32 5.7e-8
   hydrograph against the oracle (floored)               fp32 1.6e-7, fp32_flux64
@@ -62,6 +67,7 @@ pytestmark = pytest.mark.gpu
 # 1e-5 / 1e-12 of the largest entry).
 MEASURED = {
     "frames": {"float32": 5.8e-8, "float64": 9.4e-16},
+    "frames_satterlund": {"float32": 5.7e-8, "float64": 8.4e-16},  # Hum_sp, the capped plane; no plane is above it
     "clamp": {"float32": 5.6e-8, "float64": 9.4e-16},
     "many_tiles": {"float32": 5.7e-8},
     "hydrograph_floored": {"fp32": 1.6e-7, "fp32_flux64": 1.1e-7, "fp64": 5.4e-16},
@@ -151,10 +157,10 @@ def check_forcing_preconditions():
 
 
 @contextlib.contextmanager
-def forcing_engine(inp, engine, n_frames=NFRAMES, hist_depth=8, fuse=8, flux="fp32", split=None, fill=None):
+def forcing_engine(inp, engine, n_frames=NFRAMES, hist_depth=8, fuse=8, flux="fp32", split=None, fill=None, cfg=BASE_CFG):
     """An initialised engine on the bare-ice rasters with the map's ids; the
     frames zero, or `fill` in every value."""
-    e = make_engine(BASE_CFG, NY, NX, engine, n_frames=n_frames, hist_depth=hist_depth, n_catch=inp.nc, fuse_steps=fuse,
+    e = make_engine(cfg, NY, NX, engine, n_frames=n_frames, hist_depth=hist_depth, n_catch=inp.nc, fuse_steps=fuse,
                     flux=flux, split=split)
     try:
         for k in ("elev", "slope", "aspect"):
@@ -234,6 +240,64 @@ def test_frames_equal_the_restatement(engine, map_name):
         e.run(8)  # the frames as the last call left them feed a launch
         assert np.isfinite(e.get_field("M_total")).all()
     _note("frames", f"{engine}/{map_name}", worst)
+
+
+SAT_CFG = dict(BASE_CFG, SATTERLUND=True)
+
+
+@functools.lru_cache(maxsize=None)
+def check_satterlund_cap_preconditions():
+    """On the restatement alone: with SATTERLUND: true the humidity cap binds
+    in 42.6 % of the `divide` map's cell-frames, and the capped Hum_sp differs
+    from what Brutsaert's e_sat gives there by up to 6.8e-3 relative, by more
+    than 1e-4 (800 times the fp32 bound) in 93 % of them: a kernel that capped
+    with the other formula cannot pass.  Every other plane is the same."""
+    inp = _inputs()
+    sat, info = D.downscale(inp.table, inp.cid, inp.static["elev"], inp.z_ref, parts=True, cfg=SAT_CFG, **DS)
+    bru = D.downscale(inp.table, inp.cid, inp.static["elev"], inp.z_ref, **DS)
+    capped = info["rh_before"] > 1.0
+    assert 0.41 <= float(capped.mean()) <= 0.44, float(capped.mean())
+    assert not info["clamped"].any()
+    rel = np.abs(sat[:, D.I_Q, :] - bru[:, D.I_Q, :]) / np.abs(bru[:, D.I_Q, :])
+    assert float(rel[capped].max()) >= 5e-3, float(rel[capped].max())
+    assert float((rel[capped] > 1e-4).mean()) >= 0.9
+    assert all(np.array_equal(sat[:, v, :], bru[:, v, :]) for v in range(5) if v != D.I_Q)
+    assert float(D.relative_humidity(sat, D.constants(SAT_CFG)).max()) <= 1.0 + 1e-12
+    return True
+
+
+@pytest.mark.parametrize("engine", ["float32", "float64"])
+def test_satterlund_frames_equal_the_restatement(engine):
+    """SATTERLUND: true, the `divide` map, host and device tables: the humidity
+    cap of both device forcing paths takes forcing_e_sat's Satterlund branch.
+    All 24 frames within the engine's bound of the restatement under the same
+    configuration, and outside it of the Brutsaert restatement."""
+    assert check_satterlund_cap_preconditions()
+    inp = _inputs()
+    R = NP[engine]
+    worst = {}
+    with forcing_engine(inp, engine, fill=-777.0, cfg=SAT_CFG) as e:
+        elev = e.get_field("elev", dtype=R).astype(np.float64)
+        want, info = D.downscale(inp.table, inp.eff, elev, inp.z_ref, parts=True, cfg=SAT_CFG, **DS)
+        other = D.downscale(inp.table, inp.eff, elev, inp.z_ref, **DS)
+        assert 0.41 <= float((info["rh_before"] > 1).mean()) <= 0.44 and not info["clamped"].any()
+        assert frame_err(other, want)["Hum_sp"] > 1e-3  # the two restatements part by far more than the bound
+        for device in (False, True):
+            put(e, inp, inp.table, ds=_downscale(**DS), device=device)
+            got = read_frames(e, range(NFRAMES))
+            assert got.dtype == R
+            err = frame_err(got, want)
+            print(f"catchment forcing vs restatement, Satterlund, {engine} device={device}: {err}")
+            for k, v in err.items():
+                worst[k] = max(worst.get(k, 0.0), v)
+            assert max(err.values()) <= BOUND[engine], err
+            assert frame_err(got, other)["Hum_sp"] > 1e-3
+            for f in range(NFRAMES):  # the next table lands on frames it must rewrite
+                e.set_inputs(np.full((5, N), -777.0 + f), index=f)
+        put(e, inp, inp.table, ds=_downscale(**DS))
+        e.run(8)  # the frames feed a launch of the Satterlund step
+        assert np.isfinite(e.get_field("M_total")).all()
+    _note("frames_satterlund", engine, worst)
 
 
 # ------------------------------------------------------------------ 2. the precipitation clamp

@@ -30,8 +30,8 @@ import functools
 import numpy as np
 import pytest
 
-from tests.harness import (BASE_CFG, FLUX_F64_ENGINE, gpu_run_fields, make_engine, melt_out_flips, oracle_run, parity,
-                           run_gpu_vs_oracle, synthetic_inputs, valid_mask)
+from tests.harness import (BASE_CFG, FLUX_F64_ENGINE, assert_oracle_rule, gpu_run_fields, make_engine, oracle_run,
+                           run_gpu_vs_oracle, synthetic_inputs)
 
 pytestmark = pytest.mark.gpu
 
@@ -140,17 +140,7 @@ def test_satterlund_form_with_missing_forcing_vs_oracle(engine):
     outs, state, _ = gpu_run_fields(cfg, static, forcing, NY, NX, engine, nsteps)
     ref, m = oracle_run(cfg, static, forcing)
     assert np.isnan(ref["M_total"][2:, 70]).all() and np.isnan(ref["M_total"]).sum() == nsteps - 2
-    flip, genuine = melt_out_flips(outs, ref, 1e-5)
-    assert not genuine, genuine
-    ok_steps = valid_mask(flip, nsteps)
-    for v in HIST:
-        np.testing.assert_array_equal(np.isnan(outs[v]), np.isnan(ref[v]), err_msg=v)
-        ok = ~np.isnan(ref[v]) & ok_steps
-        assert parity(outs[v], np.where(np.isnan(ref[v]), 0.0, ref[v]), mask=ok)[0] <= 1e-5, v
-    for v in ("h_swe", "h_iwe", "Eccs", "Ecci", "albedo", "n"):
-        want = np.asarray(getattr(m, v), np.float64)
-        np.testing.assert_array_equal(np.isnan(state[v]), np.isnan(want), err_msg=v)
-        assert parity(state[v], want, mask=np.isfinite(want) & ok_steps[-1])[0] <= 1e-5, v
+    assert_oracle_rule(outs, state, ref, m, 1e-5)
 
 
 def test_fp64_engine_fused_equals_unfused():
